@@ -9,7 +9,21 @@
            DBSCAN, merge, global labels (labels stay in HBM).
 
   python bench.py [--gpus N --steps K --warmup W] [--config C2|C1|C3|C4]
-                  [--points N] [--no-cpu] [--no-host]
+                  [--points N] [--dump-outputs DIR] [--full [--no-cpu] [--no-host]]
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up
+steps, K timed steps, the result line (its roofline fields come from the
+timed steps' own stage times and the recorded PMC summaries, no further run).
+--full adds the legs that take runs of their own: cpu_baseline, host_input
+and one instrumented step for sweep_stats / roofline.limiter (--no-cpu and
+--no-host drop a leg from a --full run).
+
+--dump-outputs DIR writes what the last timed step returned to its caller as
+DIR/<name>.npy (float32 / float64; DIR/<name>_rank<r>.npy from rank r of an
+N-rank run): n_clusters, cluster_sizes (noise first, then every cluster, over
+all points), bounding_boxes, and labels / core_sample_mask at sample_index, a
+fixed seeded sample of the points when there are more than DUMP_SAMPLE of
+them.  The inputs are seeded, so two builds can be compared array for array.
 
 `python bench.py --gpus N` (N > 1) outside a torchrun environment starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py <same args>`
@@ -37,7 +51,7 @@ Roofline object — the neighbour-count kernel (count2_kernel, engine.hip):
   limiter: candidate tests per record and per second (the kernel's work unit).
 stage_roofline gives the link stage the same measured accounting.
 
-Other legs (single process): cpu_baseline — the reference's algorithm on the
+Other legs (single process, --full only): cpu_baseline — the reference's algorithm on the
 host cores, in a child process started before the GPU is touched
 (python -m oracle.cpu_ref); host_input — the same train from host numpy (H2D
 inside the step) and from a list of (key, vector) records.
@@ -66,6 +80,8 @@ LINK_KERNELS = ("init_kernel", "window_uf_kernel", "cell_word_root_kernel",
                 "mid_cell_word_root_kernel", "big_cell_word_root_kernel", "verify_screen_kernel",
                 "flag_list_kernel", "cell_verify_kernel", "pair_kernel")
 L2_PEAK_GBS = 34500.0            # MI355X_MICROARCH.md §L2: ~34.5 TB/s aggregate
+DUMP_SAMPLE = 1 << 21            # --dump-outputs: per-point arrays hold at most this many points
+DUMP_SEED = 20240229
 
 
 def parse():
@@ -75,8 +91,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C2")
     ap.add_argument("--points", type=int, default=None, help="override point count")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-input legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: CPU baseline, "
+                         "host-input legs, the instrumented sweep step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-host", action="store_true",
+                    help="with --full: skip the host-input legs")
     ap.add_argument("--cpu-n", type=int, default=None,
                     help="CPU baseline sample size (default 1M; 10M for C4; 20k for d > 15)")
     ap.add_argument("--json-out", default=None)
@@ -430,6 +453,34 @@ def host_legs(DBSCAN, eps, ms, P, Xh):
     return out
 
 
+def dump_outputs(dirname, m, rank, world):
+    """What the caller of the timed step received from its last call, as
+    float32 / float64 .npy files (< 64 MB in all): the whole result through
+    n_clusters, cluster_sizes and bounding_boxes; the per-point arrays at a
+    fixed seeded sample of the points (all of them up to DUMP_SAMPLE)."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    labels = m.labels_.to(torch.int64)
+    n = labels.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    at = torch.from_numpy(idx).to(labels.device)
+    boxes = m.bounding_boxes
+    arrays = {
+        "n_clusters": np.array([m.n_clusters_], np.float64),
+        "cluster_sizes": torch.bincount(labels + 1).cpu().numpy().astype(np.float64),
+        "bounding_boxes": np.array([boxes[L].as_array() for L in sorted(boxes)], np.float64),
+        "sample_index": idx.astype(np.float64),
+        "labels": labels[at].cpu().numpy().astype(np.float64),
+        "core_sample_mask": m.core_sample_mask_[at].cpu().numpy().astype(np.float32),
+    }
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -468,7 +519,7 @@ def main():
     n_cfg = args.points or cfgd["n"]
     d_cfg = cfgd["d"]
     cpu = None
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         # before the GPU is initialised, so the child inherits no HIP state
         try:
             cpu = cpu_baseline(args.config,
@@ -566,8 +617,10 @@ def main():
         tt = torch.tensor([el], dtype=torch.float64, device="cpu" if args.rehearse else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m, rank, world)
     sweep = None
-    if world == 1:   # one extra, untimed step with the instrumented sweeps
+    if world == 1 and args.full:   # one extra, untimed step with the instrumented sweeps
         ctx.set_option(_native.PD_OPT_SWEEP_STATS, 1)
         step()
         torch.cuda.synchronize()
@@ -601,7 +654,7 @@ def main():
     del m
 
     host = None
-    if world == 1 and not args.no_host and d <= 4:
+    if world == 1 and args.full and not args.no_host and d <= 4:
         host = host_legs(DBSCAN, eps, ms, P, Xh if Xh is not None else Xd.cpu().numpy())
 
     if rank == 0:

@@ -79,9 +79,11 @@ def test_launcher_runs_children_for_real(tmp_path):
     list: two ranks start, see WORLD_SIZE=2 and distinct RANKs (CPU only: the
     stand-in never imports the package)."""
     probe = tmp_path / "probe.py"
+    # one os.write per rank: the ranks share the pipe, and a line and its
+    # newline written apart can interleave with the other rank's
     probe.write_text("import os, json\n"
-                     "print(json.dumps({k: os.environ.get(k) for k in "
-                     "('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR')}), flush=True)\n")
+                     "os.write(1, (json.dumps({k: os.environ.get(k) for k in "
+                     "('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR')}) + '\\n').encode())\n")
     b = _bench()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={b._free_port()}", str(probe)]
@@ -112,6 +114,64 @@ def test_bench_gpus2_rehearse_line():
     assert rec["value"] > 0 and rec["ms_per_step"] > 0
     st = rec["shard_stats"]
     assert st["rank"] in (0, 1) and len(st["rank_seconds"]) == 2
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run asks for no leg beside the headline figure; --full asks for
+    all of them, less what --no-cpu / --no-host drop."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-host", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full is True and a.no_host is True and a.no_cpu is False and a.dump_outputs == "d"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run on a small C2 slice: none of the --full
+    legs in its line, and --dump-outputs holds what DBSCAN.train returns for
+    the same seeded points (every point: the slice is below the sample size)."""
+    import numpy as np
+    import torch
+    from pypardis_amd import DBSCAN, synth
+
+    n = 200_000
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--points", str(n),
+           "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-3000:])
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-3000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["warmup"] == 1
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - n / (rec["ms_per_step"] * 1e-3)) <= 1e-6 * rec["value"]
+    assert rec["unit"] == "points/s" and rec["higher_is_better"] is True
+    assert rec["cpu_baseline"] is None and rec["host_input"] is None
+    assert rec["sweep_stats"] is None
+
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert sorted(got) == ["bounding_boxes", "cluster_sizes", "core_sample_mask", "labels",
+                           "n_clusters", "sample_index"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+
+    X, cfg = synth.make_config("C2", n=n)
+    m = DBSCAN(eps=cfg["eps"], min_samples=cfg["min_samples"],
+               max_partitions=cfg["max_partitions"]).train(torch.from_numpy(X).to("cuda:0"))
+    lab = m.labels_.cpu().numpy().astype(np.int64)
+    assert np.array_equal(got["sample_index"], np.arange(n))
+    assert np.array_equal(got["labels"], lab)
+    assert np.array_equal(got["core_sample_mask"], m.core_sample_mask_.cpu().numpy())
+    assert got["n_clusters"].tolist() == [m.n_clusters_] and rec["n_clusters"] == m.n_clusters_
+    assert np.array_equal(got["cluster_sizes"], np.bincount(lab + 1))
+    assert len(got["cluster_sizes"]) == m.n_clusters_ + 1
+    boxes = np.array([m.bounding_boxes[L].as_array() for L in sorted(m.bounding_boxes)])
+    assert np.array_equal(got["bounding_boxes"], boxes)
 
 
 def test_train_roofline_sums_kernels_times_launches():

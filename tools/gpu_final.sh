@@ -28,7 +28,7 @@ timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.
 tail -1 $O/smoke.log
 fi
 if has c2; then
-timeout -k 10 600 python -u bench.py --steps 5 --warmup 2 --json-out $O/bench.json \
+timeout -k 10 600 python -u bench.py --full --steps 5 --warmup 2 --json-out $O/bench.json \
     > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
 echo "C2 bench ok"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o c2 \
@@ -36,7 +36,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pro
     || { tail -5 $O/prof.log; exit 1; }
 fi
 if has c4; then
-timeout -k 10 600 python -u bench.py --config C4 --steps 3 --warmup 1 --no-host \
+timeout -k 10 600 python -u bench.py --full --config C4 --steps 3 --warmup 1 --no-host \
     --json-out $O/bench_c4.json > $O/bench_c4.log 2>&1 || { tail -5 $O/bench_c4.log; exit 1; }
 echo "C4 bench ok"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c4 -o c4 \
@@ -44,7 +44,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pro
     || { tail -5 $O/prof_c4.log; exit 1; }
 fi
 if has c3; then
-timeout -k 10 400 python -u bench.py --config C3 --steps 3 --warmup 1 \
+timeout -k 10 400 python -u bench.py --full --config C3 --steps 3 --warmup 1 \
     --json-out $O/bench_c3.json > $O/bench_c3.log 2>&1 || { tail -5 $O/bench_c3.log; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o c3 \
     -- python bench.py --config C3 --steps 3 --warmup 1 --no-cpu --no-host > $O/prof_c3.log 2>&1 \
@@ -53,7 +53,7 @@ fi
 if has c1; then
 CONFIGS=C1 bash tools/gpu_pmc_all.sh > $O/pmc_c1.log 2>&1 || { tail -5 $O/pmc_c1.log; exit 1; }
 cp gpurun_out/pmc_c1_summary.json $O/ && cp gpurun_out/pmc_c1_summary.json profiles/${TAG:-r99_v99}_pmc_c1_summary.json
-timeout -k 10 300 python -u bench.py --config C1 --steps 5 --warmup 2 --no-host \
+timeout -k 10 300 python -u bench.py --full --config C1 --steps 5 --warmup 2 --no-host \
     --json-out $O/bench_c1.json > $O/bench_c1.log 2>&1 || { tail -5 $O/bench_c1.log; exit 1; }
 fi
 echo "final bench phase ok"
