@@ -519,6 +519,40 @@ int32_t pd_results(pd_ctx* ctx, int64_t nr, const uint32_t* keys, const uint8_t*
 int32_t pd_results_scatter(pd_ctx* ctx, const uint32_t* pairs, int64_t m, uint32_t gid_base,
                            int64_t n, int32_t* labels, uint8_t* core, void* stream);
 
+/* ---- Assignment of new points to trained clusters (the reference has no
+ * counterpart: its model answers only for the points it was trained on).
+ *   predict(q) = min { label(c) : c a core point, dist(q, c) <= eps }, -1 if none
+ * with the train's own predicate (fp64, axis order, every product and sum
+ * rounded separately, <= eps*eps; cityblock <= eps) and its border rule (the
+ * smallest label among the core neighbours), so querying the training points
+ * returns pd_train's labels — core, border and noise.
+ *
+ * A pd_index owns its device memory and scratch: it stays valid through any
+ * later call on `ctx` (and after pd_ctx_destroy) until pd_index_destroy.  One
+ * thread at a time may use an index. */
+typedef struct pd_index pd_index;
+
+/* cores = rows of X with core[i] != 0; labels[i] their cluster (>= 0; rows
+ * with core[i] == 0 are not read).  X / core / labels: device arrays of a
+ * finished pd_train / pd_cluster, or any caller arrays of that shape; they
+ * are not referenced after the call.  n < 2^32 - 1.  d <= 4: the cores sorted
+ * by eps-cell with a directory of the occupied cells only (memory follows the
+ * cores, not the extent); d > 4: the compacted core rows.  *n_core_host
+ * (nullable) = number of cores; 0 is valid.  PD_EINVAL: eps <= 0, a core row
+ * with a negative label or a NaN/inf coordinate.  Synchronises the stream. */
+int32_t pd_index_build(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                       const uint8_t* core, const int32_t* labels, double eps, int32_t metric,
+                       pd_index** out, int64_t* n_core_host, void* stream);
+/* out[m] (int32, input order): smallest label among the cores within eps, -1 if none.
+ * Q: device, m rows of the index's d, in the index's dtype (PD_EINVAL
+ * otherwise, and for a NaN/inf query coordinate, as the train treats its
+ * input); m == 0 is valid; m < 2^32 - 1.  d > 4: PD_EUNSUPPORTED beyond
+ * d * itemsize = 944 bytes per row (the tile kernel's LDS).  Synchronises
+ * the stream. */
+int32_t pd_index_query(pd_index* index, const void* Q, int32_t dtype, int64_t m,
+                       int32_t* out, void* stream);
+int32_t pd_index_destroy(pd_index* index);
+
 /* ---- RCCL collectives of the sharded train (one rank per device).  They
  * replace Spark's data movement: partitionBy shuffle (R:dbscan/dbscan.py:
  * 114-118) -> pd_comm_all_to_all_v; collect / broadcast of the cluster-id map

@@ -59,7 +59,8 @@ EXPORTS = ["pd_abi_version", "pd_last_error", "pd_ctx_create", "pd_ctx_destroy",
            "pd_dense_finish", "pd_kd_build", "pd_kd_labels", "pd_train_tree", "pd_kdx_begin", "pd_kdx_moments",
            "pd_kdx_axes", "pd_kdx_counts", "pd_kdx_boundary", "pd_kdx_end", "pd_route2",
            "pd_pack2", "pd_results", "pd_results_scatter", "pd_comm_exchange", "pd_comm_abort",
-           "pd_comm_self_check", "pd_comm_size"]
+           "pd_comm_self_check", "pd_comm_size", "pd_index_build", "pd_index_query",
+           "pd_index_destroy"]
 
 
 class PardisError(RuntimeError):
@@ -150,6 +151,9 @@ def load():
             "pd_comm_abort": ([P], I32),
             "pd_comm_self_check": ([P], I32),
             "pd_comm_size": ([P, P, P], I32),
+            "pd_index_build": ([P, P, I32, I64, I32, P, P, D, I32, ctypes.POINTER(P), P, P], I32),
+            "pd_index_query": ([P, P, I32, I64, P, P], I32),
+            "pd_index_destroy": ([P], I32),
         }
         for name, (args, res) in sig.items():
             f = getattr(lib, name)
@@ -486,6 +490,72 @@ def train_tree(X, eps, min_samples, metric, ebox, tree, data_box=None, want_coun
                                 core.data_ptr(), counts.data_ptr() if counts is not None else None,
                                 ncl.ctypes.data, _stream(X.device)))
     return labels, core, counts, int(ncl[0])
+
+
+# ------------------------------------------------------------ assignment index
+PD_EINVAL = -1
+
+
+class Index:
+    """pd_index: the core points of a finished train, laid out for queries.
+
+    ``X`` (n, d) device points, ``core`` (n,) uint8 / bool device mask,
+    ``labels`` (n,) int32 device labels (read on the core rows only, >= 0
+    there).  ``query(Q)`` -> int32 device tensor in the order of ``Q``: the
+    smallest label among the cores within ``eps`` of each row, -1 if none.
+    The index copies what it needs: X / core / labels may be freed, and any
+    later train on the context leaves it intact."""
+
+    def __init__(self, X, core, labels, eps, metric=PD_EUCLIDEAN, ctx=None):
+        self.ptr = None
+        dt = _check_points(X)
+        ctx = ctx or context(X.device.index)
+        n, d = X.shape
+        if core.dtype == torch.bool:
+            core = core.view(torch.uint8)
+        if core.dtype != torch.uint8 or labels.dtype != torch.int32:
+            raise TypeError("core must be uint8 / bool and labels int32")
+        if core.shape != (n,) or labels.shape != (n,):
+            raise ValueError("core and labels must have one entry per row of X")
+        if core.device != X.device or labels.device != X.device:
+            raise ValueError("X, core and labels must be on one device")
+        core, labels = core.contiguous(), labels.contiguous()
+        ptr = ctypes.c_void_p()
+        nc = np.zeros(1, np.int64)
+        _check(load().pd_index_build(ctx.ptr, X.data_ptr() if n else None, dt, n, d,
+                                     core.data_ptr() if n else None,
+                                     labels.data_ptr() if n else None, float(eps), int(metric),
+                                     ctypes.byref(ptr), nc.ctypes.data, _stream(X.device)))
+        self.ptr = ptr
+        self.device = X.device
+        self.dtype = X.dtype
+        self.d = int(d)
+        self.n_core = int(nc[0])
+
+    def query(self, Q):
+        if self.ptr is None:
+            raise ValueError("the index was closed")
+        dt = _check_points(Q)
+        if Q.shape[1] != self.d:
+            raise ValueError(f"queries have {Q.shape[1]} columns, the index was built on {self.d}")
+        if Q.device != self.device:
+            raise ValueError(f"queries are on {Q.device}, the index on {self.device}")
+        m = Q.shape[0]
+        out = torch.empty(m, dtype=torch.int32, device=Q.device)
+        _check(load().pd_index_query(self.ptr, Q.data_ptr() if m else None, dt, m,
+                                     out.data_ptr() if m else None, _stream(Q.device)))
+        return out
+
+    def close(self):
+        ptr, self.ptr = self.ptr, None
+        if ptr:
+            load().pd_index_destroy(ptr)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ------------------------------------------------------- sharded train stages

@@ -71,6 +71,10 @@ struct pd_comm {
     pd::Comm* c;
 };
 
+struct pd_index {
+    pd::Index* ix;
+};
+
 namespace pd {
 template <typename F>
 static int32_t comm_guard(pd_comm* comm, F&& f) {
@@ -792,6 +796,39 @@ int32_t pd_dense_finish(pd_ctx* ctx, const int32_t* best, int32_t* labels, uint8
         const int64_t ncl = dense_finish(ctx->c, best, labels, core, counts, (hipStream_t)stream);
         if (n_clusters) *n_clusters = ncl;
     });
+}
+
+// ---------------------------------------------------------------- assignment index
+
+int32_t pd_index_build(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                       const uint8_t* core, const int32_t* labels, double eps, int32_t metric,
+                       pd_index** out, int64_t* n_core, void* stream) {
+    return guard(ctx, [&] {
+        check_common(ctx, X, n, d);
+        if (!out) throw Error(PD_EINVAL, "null out");
+        if (n > 0 && (!core || !labels)) throw Error(PD_EINVAL, "null core / labels");
+        pd::Index* ix = index_build(ctx->c.device, X, dtype, n, d, core, labels, eps, metric,
+                                    (hipStream_t)stream);
+        *out = new pd_index{ix};
+        if (n_core) *n_core = index_cores(ix);
+    });
+}
+
+int32_t pd_index_query(pd_index* index, const void* Q, int32_t dtype, int64_t m, int32_t* out,
+                       void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        if (m < 0 || (m && (!Q || !out))) throw Error(PD_EINVAL, "bad query arrays");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_query(index->ix, Q, dtype, m, out, (hipStream_t)stream);
+    });
+}
+
+int32_t pd_index_destroy(pd_index* index) {
+    if (!index) return PD_OK;
+    int32_t rc = guard(nullptr, [&] { index_destroy(index->ix); });
+    delete index;
+    return rc;
 }
 
 // ---------------------------------------------------------------- RCCL

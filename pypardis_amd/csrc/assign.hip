@@ -1,0 +1,772 @@
+// Assignment of new points to the clusters of a finished train (pd_index_*).
+//
+//   predict(q) = min { label(c) : c core, dist(q, c) <= eps }     (-1: none)
+//
+// with the train's own predicate (pred.hpp) and the train's border rule (a
+// border point takes the smallest key among its core neighbours, and labels
+// rank the keys), so predict(X_train) == labels_ for core, border and noise
+// points alike.
+//
+// The index owns its device memory (`keep`) and a private scratch context
+// (`work`: sort buffers, compaction offsets, the pinned block), so no train on
+// the caller's context can touch it.
+//
+// d <= 4 — a grid over the cores' tight bounding box, cells eps*(1 + 2^-20)
+// wide on every axis (any pair the predicate accepts lies in adjacent cells):
+//   Xs    T[nc * S]     core coordinates in cell order (S: Stride<D>)
+//   lab   i32[nc]       their labels
+//   ckey  K[ncells]     keys of the OCCUPIED cells, ascending (row-major, axis 0
+//                       fastest)
+//   cstart u32[ncells+1] first core of each occupied cell
+//   clab  i32[ncells]   the label every core of the cell has, -1 when they differ
+//   tab   u32[ntab]     lower bound in ckey of every key prefix (key >> shift)
+// Memory follows the cores, never the extent: two blobs 1e6 apart cost what the
+// blobs cost.  A query walks the 3^(d-1) rows around its cell; in each the
+// (up to) three neighbour cells are one contiguous key run [k0, k1], found by
+// one bucketed binary search over ckey, and their cores one contiguous record
+// run.  Only a label below the best one so far can change the answer: a cell
+// whose cores all share a label not below it is skipped whole, one that shares
+// a smaller label is decided by its first hit, and in a mixed cell only the
+// cores with a smaller label are tested (C2, the 1e8 training points: sweep
+// kernel 34.8 -> 11.3 ms).  Cells grow by a common factor (exact at any width >= eps) only to keep
+// every axis below 2^28 cells — the bound under which the fp64 rounding of the
+// cell coordinate stays inside the 2^-20 margin — and the key below 2^62.
+//
+// d > 4 — the compacted core rows, swept as LDS tiles by every query
+// (exact fp64, axis order; no MFMA screen: DESIGN.md §10).
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
+
+#include "compact.hpp"
+#include "internal.hpp"
+#include "pred.hpp"
+
+namespace pd {
+
+struct IxGrid {
+    double lo[kMaxDim];       // origin: the cores' tight bbox
+    double inv[kMaxDim];      // 1 / cell side
+    int64_t nc[kMaxDim];      // cells per axis
+    uint64_t stride[kMaxDim]; // key = sum c[j] * stride[j]
+    uint64_t G;               // cells in all (also: the key of a query nothing can match)
+};
+
+struct Index {
+    Ctx work;                 // scratch only
+    Arena keep;               // what a query reads
+    int device = 0, dtype = 0, d = 0, metric = 0;
+    double eps = 0;
+    uint64_t nc = 0;          // core points
+    IxGrid g{};
+    int key_bytes = 4, key_bits = 1, shift = 0;
+    uint32_t ncells = 0;
+    uint64_t ntab = 0;
+    float slo = -1.0f, shi = INFINITY;
+    void* Xs = nullptr;       // d <= 4: cell order, Stride<D>; d > 4: compacted rows
+    int32_t* lab = nullptr;
+    void* ckey = nullptr;
+    uint32_t* cstart = nullptr;
+    int32_t* clab = nullptr;
+    uint32_t* tab = nullptr;
+};
+
+namespace {
+
+// Queries per call from which they are swept in cell order (key, sort, sweep
+// through the order) instead of input order: measured on C2 (tools/
+// predict_bench.py, ms sorted / direct) 65536: 0.16 / 0.10, 262144: 0.22 /
+// 0.21, 1e6: 0.43 / 0.99, 1e8: 14.1 / 178.  PD_INDEX_SORT_MIN overrides it per
+// call (that A/B, and the tests; same results either way).
+constexpr uint64_t kSortMin = 1 << 18;
+uint64_t sort_min() {
+    const char* e = std::getenv("PD_INDEX_SORT_MIN");
+    if (!e || !*e) return kSortMin;
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    return end && *end == 0 ? (uint64_t)v : kSortMin;
+}
+constexpr int64_t kMaxAxisCells = 1ll << 28;
+constexpr int kStatSlots = 2 + 2 * kMaxDim;  // non-finite, negative labels, min[4], max[4]
+
+struct CorePred {
+    const uint8_t* core;
+    __device__ bool operator()(uint32_t i) const { return core[i] != 0; }
+};
+
+template <typename K>
+struct HeadPred {
+    const K* keys;
+    __device__ bool operator()(uint32_t i) const { return i == 0 || keys[i] != keys[i - 1]; }
+};
+
+// order-preserving u64 image of a double (for atomicMin / atomicMax)
+__device__ __forceinline__ unsigned long long enc_f64(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+inline double dec_f64(unsigned long long e) {
+    const unsigned long long u = (e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
+    double v;
+    std::memcpy(&v, &u, sizeof(v));
+    return v;
+}
+
+// Non-finite coordinates and negative labels among the core rows; for
+// d <= kMaxDim also their tight bbox.  stats: see kStatSlots (min slots start
+// at ~0, max slots at 0).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void core_stats_kernel(const T* __restrict__ X, int d,
+                                                            const uint32_t* __restrict__ clist,
+                                                            uint64_t nc,
+                                                            const int32_t* __restrict__ labels,
+                                                            unsigned long long* __restrict__ stats) {
+    const bool box = d <= kMaxDim;
+    double mn[kMaxDim], mx[kMaxDim];
+#pragma unroll
+    for (int j = 0; j < kMaxDim; ++j) {
+        mn[j] = INFINITY;
+        mx[j] = -INFINITY;
+    }
+    unsigned bad = 0, neg = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nc;
+         i += (uint64_t)gridDim.x * kBlock) {
+        const uint64_t p = clist[i];
+        neg += labels[p] < 0 ? 1u : 0u;
+        if (box) {
+#pragma unroll
+            for (int j = 0; j < kMaxDim; ++j) {
+                if (j < d) {
+                    const double v = (double)X[p * d + j];
+                    if (!isfinite(v)) {
+                        ++bad;
+                    } else {
+                        mn[j] = fmin(mn[j], v);
+                        mx[j] = fmax(mx[j], v);
+                    }
+                }
+            }
+        } else {
+            for (int j = 0; j < d; ++j) bad += isfinite((double)X[p * d + j]) ? 0u : 1u;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        bad += (unsigned)__shfl_xor((int)bad, o, 64);
+        neg += (unsigned)__shfl_xor((int)neg, o, 64);
+#pragma unroll
+        for (int j = 0; j < kMaxDim; ++j) {
+            mn[j] = fmin(mn[j], __shfl_xor(mn[j], o, 64));
+            mx[j] = fmax(mx[j], __shfl_xor(mx[j], o, 64));
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (bad) atomicAdd(stats + 0, (unsigned long long)bad);
+        if (neg) atomicAdd(stats + 1, (unsigned long long)neg);
+        if (box) {
+            for (int j = 0; j < d; ++j) {
+                if (mn[j] <= mx[j]) {
+                    atomicMin(stats + 2 + j, enc_f64(mn[j]));
+                    atomicMax(stats + 2 + kMaxDim + j, enc_f64(mx[j]));
+                }
+            }
+        }
+    }
+}
+
+// Cell coordinate of v along every axis, in the arithmetic the host sized the
+// grid with: floor((v - lo) * inv), each operation rounded on its own.
+// Returns false when v lies more than one cell outside the grid (nothing can
+// be within eps of it); otherwise c[j] is in [-1, nc[j]].
+template <int D>
+__device__ __forceinline__ bool cell_of(const double (&v)[D], const IxGrid& g, int64_t (&c)[D]) {
+    bool in = true;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        const double s = __dmul_rn(__dadd_rn(v[j], -g.lo[j]), g.inv[j]);
+        const bool ok = (s >= -1.0) && (s < (double)g.nc[j] + 1.0);
+        in = in && ok;
+        c[j] = ok ? (int64_t)floor(s) : 0;
+    }
+    return in;
+}
+
+template <int D>
+__device__ __forceinline__ uint64_t clamped_key(const int64_t (&c)[D], const IxGrid& g) {
+    uint64_t k = 0;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        int64_t q = c[j] < 0 ? 0 : c[j];
+        q = q >= g.nc[j] ? g.nc[j] - 1 : q;
+        k += (uint64_t)q * g.stride[j];
+    }
+    return k;
+}
+
+template <typename T, int D, typename K>
+__global__ __launch_bounds__(kBlock) void core_key_kernel(const T* __restrict__ X,
+                                                          const uint32_t* __restrict__ clist,
+                                                          uint64_t nc, IxGrid g,
+                                                          K* __restrict__ keys,
+                                                          uint32_t* __restrict__ vals) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nc) return;
+    const uint64_t p = clist[i];
+    double v[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) v[j] = (double)X[p * D + j];
+    int64_t c[D];
+    (void)cell_of<D>(v, g, c);   // a core is inside the box: always in
+    keys[i] = (K)clamped_key<D>(c, g);
+    vals[i] = (uint32_t)i;
+}
+
+// Coordinates (Stride<D> layout, pad 0) and labels into cell order.
+template <typename T, int D>
+__global__ __launch_bounds__(kBlock) void core_gather_kernel(const T* __restrict__ X,
+                                                             const uint32_t* __restrict__ clist,
+                                                             const uint32_t* __restrict__ vals,
+                                                             const int32_t* __restrict__ labels,
+                                                             uint64_t nc, T* __restrict__ Xs,
+                                                             int32_t* __restrict__ lab) {
+    constexpr int S = Stride<D>::v;
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= nc) return;
+    const uint64_t p = clist[vals[r]];
+#pragma unroll
+    for (int j = 0; j < S; ++j) Xs[r * S + j] = j < D ? X[p * D + j] : (T)0;
+    lab[r] = labels[p];
+}
+
+// d > kMaxDim: the compacted rows as they are.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void rows_gather_kernel(const T* __restrict__ X, int d,
+                                                             const uint32_t* __restrict__ clist,
+                                                             const int32_t* __restrict__ labels,
+                                                             uint64_t nc, T* __restrict__ Xc,
+                                                             int32_t* __restrict__ lab) {
+    const uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= nc * (uint64_t)d) return;
+    const uint64_t r = e / (uint64_t)d, k = e % (uint64_t)d;
+    const uint64_t p = clist[r];
+    Xc[e] = X[p * d + k];
+    if (k == 0) lab[r] = labels[p];
+}
+
+// ckey[c] = key of occupied cell c; cstart gets its end sentinel.
+template <typename K>
+__global__ __launch_bounds__(kBlock) void cell_keys_kernel(const K* __restrict__ keys,
+                                                           uint32_t* __restrict__ cstart,
+                                                           uint32_t ncells, uint32_t nc,
+                                                           K* __restrict__ ckey) {
+    const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c < ncells) ckey[c] = keys[cstart[c]];
+    if (c == ncells) cstart[c] = nc;
+}
+
+// clab[c] = the label all cores of cell c share, -1 when they differ.
+__global__ __launch_bounds__(kBlock) void cell_label_kernel(const uint32_t* __restrict__ cstart,
+                                                            const int32_t* __restrict__ lab,
+                                                            uint32_t ncells,
+                                                            int32_t* __restrict__ clab) {
+    const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= ncells) return;
+    const uint32_t j1 = cstart[c + 1];
+    uint32_t j = cstart[c];
+    const int32_t l = lab[j];
+    for (++j; j < j1 && lab[j] == l; ++j) {}
+    clab[c] = j == j1 ? l : -1;
+}
+
+template <typename K>
+__device__ __forceinline__ uint32_t cell_lower_bound(const K* __restrict__ ckey, uint32_t lo,
+                                                uint32_t hi, uint64_t k) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((uint64_t)ckey[mid] < k)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// tab[b] = first occupied cell whose key is >= b << shift.
+template <typename K>
+__global__ __launch_bounds__(kBlock) void cell_tab_kernel(const K* __restrict__ ckey,
+                                                          uint32_t ncells, int shift,
+                                                          uint64_t ntab,
+                                                          uint32_t* __restrict__ tab) {
+    const uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (b >= ntab) return;
+    tab[b] = cell_lower_bound<K>(ckey, 0u, ncells, b << shift);
+}
+
+// Key of each query's own (clamped) cell; G for a query nothing can match.
+template <typename T, int D, typename K>
+__global__ __launch_bounds__(kBlock) void query_key_kernel(const T* __restrict__ Q, uint64_t m,
+                                                           IxGrid g, K* __restrict__ keys,
+                                                           uint32_t* __restrict__ vals) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    double v[D];
+    bool fin = true;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        v[j] = (double)Q[i * D + j];
+        fin = fin && isfinite(v[j]);
+    }
+    int64_t c[D];
+    const bool in = fin && cell_of<D>(v, g, c);
+    keys[i] = in ? (K)clamped_key<D>(c, g) : (K)g.G;
+    vals[i] = (uint32_t)i;
+}
+
+template <int D>
+struct Rows {
+    static constexpr int v = D == 1 ? 1 : D == 2 ? 3 : D == 3 ? 9 : 27;
+};
+
+// One lane per query: the 3^(D-1) neighbour rows, the query's own first, each
+// one key run of <= 3 occupied cells; fp32 screen + exact fp64 recheck (Pred)
+// of the cores whose label could lower the answer; the smallest label among
+// the hits.  order (nullable): lane i sweeps query
+// order[i] (the queries sorted by cell), results go back to input order.
+template <typename T, int D, int M, typename K>
+__global__ __launch_bounds__(kBlock) void query_kernel(
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxGrid g,
+    const T* __restrict__ Xs, const int32_t* __restrict__ lab, const K* __restrict__ ckey,
+    const uint32_t* __restrict__ cstart, const int32_t* __restrict__ clab,
+    const uint32_t* __restrict__ tab, uint32_t ncells, int shift, double eps, double eps2, float slo, float shi, int32_t* __restrict__ out,
+    unsigned long long* __restrict__ bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t qi = order ? (uint64_t)order[i] : i;
+    Pred<T, D, M> pr;
+    bool fin = true;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        pr.ar[j] = Q[qi * D + j];
+        pr.a[j] = (double)pr.ar[j];
+        fin = fin && isfinite(pr.a[j]);
+    }
+    pr.eps = eps;
+    pr.eps2 = eps2;
+    pr.lo = slo;
+    pr.hi = shi;
+    if (!fin) {
+        atomicAdd(bad, 1ull);
+        out[qi] = -1;
+        return;
+    }
+    int64_t c[D];
+    if (!cell_of<D>(pr.a, g, c)) {   // outside the cores' box grown by a cell
+        out[qi] = -1;
+        return;
+    }
+    const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
+    const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
+    int32_t best = INT32_MAX;
+    for (int rq = 0; rq < Rows<D>::v; ++rq) {
+        // the query's own row first: its first hit usually settles every cell
+        // of the same cluster
+        const int r = (rq + Rows<D>::v / 2) % Rows<D>::v;
+        uint64_t base = 0;
+        bool ok = true;
+        int rr = r;
+#pragma unroll
+        for (int a = D - 1; a >= 1; --a) {
+            // r in base 3, axis D-1 the most significant digit
+            int pw = 1;
+            for (int t = 1; t < a; ++t) pw *= 3;
+            const int64_t y = c[a] + (int64_t)(rr / pw) - 1;
+            rr %= pw;
+            ok = ok && y >= 0 && y < g.nc[a];
+            base += (uint64_t)(ok ? y : 0) * g.stride[a];
+        }
+        if (!ok) continue;
+        const uint64_t klo = base + (uint64_t)x0, khi = base + (uint64_t)x1;
+        const uint64_t b = klo >> shift;
+        uint32_t e = cell_lower_bound<K>(ckey, tab[b], tab[b + 1], klo);
+        for (; e < ncells && (uint64_t)ckey[e] <= khi; ++e) {   // <= 3 cells
+            const int32_t cl = clab[e];
+            const uint32_t j1 = cstart[e + 1];
+            uint32_t j = cstart[e];
+            if (cl >= 0) {
+                if (cl >= best) continue;
+                for (; j < j1; ++j) {
+                    T bv[D];
+                    load_raw<T, D>(Xs, j, bv);
+                    if (pr(bv)) {
+                        best = cl;
+                        break;
+                    }
+                }
+            } else {
+                for (; j < j1; ++j) {
+                    const int32_t l = lab[j];
+                    if (l >= best) continue;
+                    T bv[D];
+                    load_raw<T, D>(Xs, j, bv);
+                    if (pr(bv)) best = l;
+                }
+            }
+        }
+    }
+    out[qi] = best == INT32_MAX ? -1 : best;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void finite_kernel(const T* __restrict__ Q, uint64_t total,
+                                                        unsigned long long* __restrict__ bad) {
+    unsigned c = 0;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < total;
+         e += (uint64_t)gridDim.x * kBlock)
+        c += isfinite((double)Q[e]) ? 0u : 1u;
+    if (c) atomicAdd(bad, (unsigned long long)c);
+}
+
+// d > kMaxDim.  A block of QB lanes owns QB queries, kept transposed in LDS
+// (Qs[k][lane]: conflict-free); the core rows pass through LDS in tiles of TC
+// (every lane reads the same core element: a broadcast).  Each pair runs the
+// predicate's own fp64 sum in axis order (within_axis) and stops at the first
+// partial sum above the threshold — the sum never decreases, so the outcome is
+// that of the full sum.
+template <typename T, int M>
+__global__ __launch_bounds__(kBlock) void dense_query_kernel(
+    const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc,
+    const int32_t* __restrict__ lab, uint64_t nc, int TC, double thr, int32_t* __restrict__ out,
+    unsigned long long* __restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
+    T* Qs = reinterpret_cast<T*>(smem);
+    T* Cs = Qs + (size_t)d * QB;
+    int32_t* Ls = reinterpret_cast<int32_t*>(Cs + (size_t)TC * d);
+    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
+    unsigned nf = 0;
+    for (int e = tid; e < QB * d; e += QB) {
+        const int row = e / d, k = e % d;
+        const uint64_t gi = q0 + (uint64_t)row;
+        const T v = gi < m ? Q[gi * (uint64_t)d + k] : (T)0;
+        nf += isfinite((double)v) ? 0u : 1u;
+        Qs[(size_t)k * QB + row] = v;
+    }
+    if (nf) atomicAdd(bad, (unsigned long long)nf);
+    int32_t best = INT32_MAX;
+    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
+        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
+        __syncthreads();
+        for (int e = tid; e < tc * d; e += QB) Cs[e] = Xc[t0 * (uint64_t)d + e];
+        for (int e = tid; e < tc; e += QB) Ls[e] = lab[t0 + e];
+        __syncthreads();
+        for (int c = 0; c < tc; ++c) {
+            const T* cr = Cs + (size_t)c * d;
+            double acc = 0.0;
+            for (int k = 0; k < d; ++k) {
+                acc = within_axis<M>(acc, (double)Qs[(size_t)k * QB + tid], (double)cr[k]);
+                if (acc > thr) break;
+            }
+            if (acc <= thr) {
+                const int32_t l = Ls[c];
+                best = l < best ? l : best;
+            }
+        }
+    }
+    const uint64_t gi = q0 + (uint64_t)tid;
+    if (gi < m) out[gi] = best == INT32_MAX ? -1 : best;
+}
+
+inline unsigned blocks(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+uint64_t read_u64(Ctx& w, const unsigned long long* dev, int count, unsigned long long* host_out,
+                  hipStream_t s) {
+    unsigned long long* h = (unsigned long long*)pinned(w, sizeof(unsigned long long) * count);
+    PD_HIP(hipMemcpyAsync(h, dev, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, s));
+    sync(s);
+    for (int i = 0; i < count; ++i) host_out[i] = h[i];
+    return host_out[0];
+}
+
+// The grid over [lo, hi]: cells eps*(1 + 2^-20)*grow wide, grow doubled until
+// every axis has <= 2^28 cells and the key stays below 2^62.
+void size_grid(Index& ix, const double* lo, const double* hi) {
+    const int d = ix.d;
+    double grow = 1.0;
+    for (int attempt = 0;; ++attempt) {
+        const double cw = ix.eps * (1.0 + 1.0 / 1048576.0) * grow;
+        const double inv = 1.0 / cw;
+        bool ok = std::isfinite(cw) && inv > 0.0;
+        long double G = 1;
+        for (int j = 0; j < d && ok; ++j) {
+            const double nc = std::floor((hi[j] - lo[j]) * inv) + 1.0;
+            if (!(nc >= 1.0 && nc <= (double)kMaxAxisCells)) {
+                ok = false;
+                break;
+            }
+            ix.g.lo[j] = lo[j];
+            ix.g.inv[j] = inv;
+            ix.g.nc[j] = (int64_t)nc;
+            G *= (long double)nc;
+        }
+        if (ok && G < 4.0e18L) {
+            uint64_t st = 1;
+            for (int j = 0; j < d; ++j) {
+                ix.g.stride[j] = st;
+                st *= (uint64_t)ix.g.nc[j];
+            }
+            ix.g.G = st;
+            break;
+        }
+        if (attempt >= 2200)
+            throw Error(-5, "pd_index_build: no cell size fits the cores' extent");
+        grow *= 2.0;
+    }
+    ix.key_bits = 1;
+    while (ix.key_bits < 64 && (ix.g.G >> ix.key_bits)) ++ix.key_bits;
+    ix.key_bytes = ix.g.G < 0xFFFFFFFFull ? 4 : 8;
+}
+
+void drop_scratch(Index& ix) {
+    ix.work.arena.release();
+    ix.work.rs_look = nullptr;   // the sort's look-back words went with the arena
+    ix.work.rs_look_tiles = 0;
+    ix.work.rs_epoch = 0;
+}
+
+template <typename T, int D, typename K>
+void build_grid(Index& ix, const T* X, const uint32_t* clist, const int32_t* labels,
+                hipStream_t s) {
+    constexpr int S = Stride<D>::v;
+    Ctx& w = ix.work;
+    const uint64_t nc = ix.nc;
+    K* keys = w.arena.get<K>("ix_keys", nc);
+    uint32_t* vals = w.arena.get<uint32_t>("ix_vals", nc);
+    hipLaunchKernelGGL((core_key_kernel<T, D, K>), dim3(blocks(nc)), dim3(kBlock), 0, s, X, clist,
+                       nc, ix.g, keys, vals);
+    PD_HIP(hipGetLastError());
+    sort_pairs_inplace(w, keys, (int)sizeof(K), vals, nc, ix.key_bits, s);
+    T* Xs = ix.keep.get<T>("Xs", nc * S);
+    ix.lab = ix.keep.get<int32_t>("lab", nc);
+    hipLaunchKernelGGL((core_gather_kernel<T, D>), dim3(blocks(nc)), dim3(kBlock), 0, s, X, clist,
+                       vals, labels, nc, Xs, ix.lab);
+    ix.Xs = Xs;
+    uint32_t* heads = w.arena.get<uint32_t>("ix_heads", nc + 1);
+    const uint64_t ncells =
+        compact_ordered(w, "ix_h", nc, HeadPred<K>{keys}, heads, nullptr, s);   // syncs
+    ix.ncells = (uint32_t)ncells;
+    ix.cstart = ix.keep.get<uint32_t>("cstart", ncells + 1);
+    PD_HIP(hipMemcpyAsync(ix.cstart, heads, sizeof(uint32_t) * ncells, hipMemcpyDeviceToDevice, s));
+    K* ckey = ix.keep.get<K>("ckey", ncells);
+    hipLaunchKernelGGL((cell_keys_kernel<K>), dim3(blocks(ncells + 1)), dim3(kBlock), 0, s, keys,
+                       ix.cstart, ix.ncells, (uint32_t)nc, ckey);
+    ix.ckey = ckey;
+    ix.clab = ix.keep.get<int32_t>("clab", ncells);
+    hipLaunchKernelGGL(cell_label_kernel, dim3(blocks(ncells)), dim3(kBlock), 0, s, ix.cstart,
+                       ix.lab, ix.ncells, ix.clab);
+    // key prefixes: about two per occupied cell, 2^8 .. 2^22 of them
+    int cb = 1;
+    while (cb < 32 && (ncells >> cb)) ++cb;
+    const int tb = std::min(22, std::max(8, cb + 1));
+    int kb = 1;
+    while (kb < 64 && ((ix.g.G - 1) >> kb)) ++kb;
+    ix.shift = kb > tb ? kb - tb : 0;
+    ix.ntab = ((ix.g.G - 1) >> ix.shift) + 2;
+    ix.tab = ix.keep.get<uint32_t>("tab", ix.ntab);
+    hipLaunchKernelGGL((cell_tab_kernel<K>), dim3(blocks(ix.ntab)), dim3(kBlock), 0, s, ckey,
+                       ix.ncells, ix.shift, ix.ntab, ix.tab);
+    PD_HIP(hipGetLastError());
+}
+
+template <typename T, typename K>
+void build_grid_d(Index& ix, const T* X, const uint32_t* clist, const int32_t* labels,
+                  hipStream_t s) {
+    switch (ix.d) {
+        case 1: build_grid<T, 1, K>(ix, X, clist, labels, s); break;
+        case 2: build_grid<T, 2, K>(ix, X, clist, labels, s); break;
+        case 3: build_grid<T, 3, K>(ix, X, clist, labels, s); break;
+        default: build_grid<T, 4, K>(ix, X, clist, labels, s); break;
+    }
+}
+
+template <typename T>
+void build_t(Index& ix, const T* X, int64_t n, const uint8_t* core, const int32_t* labels,
+             hipStream_t s) {
+    Ctx& w = ix.work;
+    const int d = ix.d;
+    uint32_t* clist = w.arena.get<uint32_t>("ix_clist", (size_t)n);
+    ix.nc = compact_ordered(w, "ix_c", (uint64_t)n, CorePred{core}, clist, nullptr, s);   // syncs
+    if (ix.nc == 0) return;
+    unsigned long long init[kStatSlots], st[kStatSlots];
+    for (int i = 0; i < kStatSlots; ++i) init[i] = (i >= 2 && i < 2 + kMaxDim) ? ~0ull : 0ull;
+    unsigned long long* stats = w.arena.get<unsigned long long>("ix_stats", kStatSlots);
+    PD_HIP(hipMemcpyAsync(stats, init, sizeof(init), hipMemcpyHostToDevice, s));
+    sync(s);   // init is a stack array
+    hipLaunchKernelGGL((core_stats_kernel<T>), dim3(grid_for((int64_t)ix.nc, 1024)), dim3(kBlock),
+                       0, s, X, d, clist, ix.nc, labels, stats);
+    PD_HIP(hipGetLastError());
+    read_u64(w, stats, kStatSlots, st, s);
+    if (st[0]) throw Error(-1, "pd_index_build: a core point has a NaN or infinite coordinate");
+    if (st[1]) throw Error(-1, "pd_index_build: a core point has a negative label");
+    if (d > kMaxDim) {
+        T* Xc = ix.keep.get<T>("Xs", ix.nc * (size_t)d);
+        ix.lab = ix.keep.get<int32_t>("lab", ix.nc);
+        hipLaunchKernelGGL((rows_gather_kernel<T>), dim3(blocks(ix.nc * (uint64_t)d)), dim3(kBlock),
+                           0, s, X, d, clist, labels, ix.nc, Xc, ix.lab);
+        PD_HIP(hipGetLastError());
+        ix.Xs = Xc;
+        return;
+    }
+    double lo[kMaxDim], hi[kMaxDim];
+    for (int j = 0; j < d; ++j) {
+        lo[j] = dec_f64(st[2 + j]);
+        hi[j] = dec_f64(st[2 + kMaxDim + j]);
+    }
+    size_grid(ix, lo, hi);
+    if (ix.key_bytes == 4)
+        build_grid_d<T, uint32_t>(ix, X, clist, labels, s);
+    else
+        build_grid_d<T, uint64_t>(ix, X, clist, labels, s);
+}
+
+template <typename T, int D, int M, typename K>
+void query_grid(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
+                hipStream_t s) {
+    Ctx& w = ix.work;
+    const uint32_t* order = nullptr;
+    if (m >= sort_min()) {
+        K* keys = w.arena.get<K>("q_keys", m);
+        uint32_t* vals = w.arena.get<uint32_t>("q_vals", m);
+        hipLaunchKernelGGL((query_key_kernel<T, D, K>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m,
+                           ix.g, keys, vals);
+        PD_HIP(hipGetLastError());
+        sort_pairs_inplace(w, keys, (int)sizeof(K), vals, m, ix.key_bits, s);
+        order = vals;
+    }
+    hipLaunchKernelGGL((query_kernel<T, D, M, K>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m, order,
+                       ix.g, (const T*)ix.Xs, ix.lab, (const K*)ix.ckey, ix.cstart, ix.clab, ix.tab,
+                       ix.ncells, ix.shift, ix.eps, ix.eps * ix.eps, ix.slo, ix.shi, out, bad);
+    PD_HIP(hipGetLastError());
+}
+
+template <typename T, int D, int M>
+void query_grid_k(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
+                  hipStream_t s) {
+    if (ix.key_bytes == 4)
+        query_grid<T, D, M, uint32_t>(ix, Q, m, out, bad, s);
+    else
+        query_grid<T, D, M, uint64_t>(ix, Q, m, out, bad, s);
+}
+
+template <typename T, int M>
+void query_dense(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
+                 hipStream_t s) {
+    // LDS: QB query rows (<= 32 KiB where a block size allows it) + TC core
+    // rows and labels, 60 KiB in all
+    const size_t row = (size_t)ix.d * sizeof(T);
+    int QB = 256;
+    while (QB > 64 && (size_t)QB * row > (32u << 10)) QB >>= 1;
+    const size_t budget = 60u << 10;
+    if ((size_t)QB * row + row + 4 > budget)
+        throw Error(-5, "pd_index_query: d too large for the tile kernel's LDS (d * itemsize <= 944)");
+    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * row) / (row + 4));
+    const size_t lds = (size_t)QB * row + (size_t)TC * (row + 4);
+    const double thr = M == 0 ? ix.eps * ix.eps : ix.eps;
+    hipLaunchKernelGGL((dense_query_kernel<T, M>), dim3((unsigned)((m + QB - 1) / QB)), dim3(QB),
+                       lds, s, Q, m, ix.d, (const T*)ix.Xs, ix.lab, ix.nc, TC, thr, out, bad);
+    PD_HIP(hipGetLastError());
+}
+
+template <typename T, int M>
+void query_m(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
+             hipStream_t s) {
+    switch (ix.d) {
+        case 1: query_grid_k<T, 1, M>(ix, Q, m, out, bad, s); break;
+        case 2: query_grid_k<T, 2, M>(ix, Q, m, out, bad, s); break;
+        case 3: query_grid_k<T, 3, M>(ix, Q, m, out, bad, s); break;
+        case 4: query_grid_k<T, 4, M>(ix, Q, m, out, bad, s); break;
+        default: query_dense<T, M>(ix, Q, m, out, bad, s); break;
+    }
+}
+
+template <typename T>
+void query_t(Index& ix, const T* Q, uint64_t m, int32_t* out, hipStream_t s) {
+    Ctx& w = ix.work;
+    unsigned long long* bad = w.arena.get<unsigned long long>("q_bad", 1);
+    PD_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
+    if (ix.nc == 0) {
+        hipLaunchKernelGGL((finite_kernel<T>), dim3(grid_for((int64_t)(m * ix.d), 1024)),
+                           dim3(kBlock), 0, s, Q, m * (uint64_t)ix.d, bad);
+        PD_HIP(hipGetLastError());
+        PD_HIP(hipMemsetAsync(out, 0xFF, sizeof(int32_t) * m, s));   // -1
+    } else if (ix.metric == 0) {
+        query_m<T, 0>(ix, Q, m, out, bad, s);
+    } else {
+        query_m<T, 1>(ix, Q, m, out, bad, s);
+    }
+    unsigned long long nbad = 0;
+    read_u64(w, bad, 1, &nbad, s);
+    if (nbad) throw Error(-1, "pd_index_query: a query has a NaN or infinite coordinate");
+}
+
+}  // namespace
+
+Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const uint8_t* core,
+                   const int32_t* labels, double eps, int metric, hipStream_t s) {
+    if (!(eps > 0) || !std::isfinite(eps)) throw Error(-1, "eps must be a finite value > 0");
+    if (metric != 0 && metric != 1) throw Error(-1, "metric must be 0 (euclidean) or 1 (cityblock)");
+    if (dtype != 0 && dtype != 1) throw Error(-1, "dtype must be 0 (float32) or 1 (float64)");
+    if (n >= 0xFFFFFFFFll) throw Error(-5, "pd_index_build: n must be < 2^32 - 1");
+    Index* ix = new Index();
+    ix->device = ix->work.device = device;
+    ix->dtype = dtype;
+    ix->d = d;
+    ix->metric = metric;
+    ix->eps = eps;
+    // fp32 screening band (see Pred): thresholds rounded outward
+    const double thr = metric == 0 ? eps * eps : eps;
+    if (dtype == 0 && thr > 1e-30 && thr < 1e30) {
+        ix->slo = std::nextafter((float)(thr * (1.0 - 1.0 / 262144.0)), 0.0f);
+        ix->shi = std::nextafter((float)(thr * (1.0 + 1.0 / 262144.0)), INFINITY);
+    }
+    try {
+        if (n > 0) {
+            if (dtype == 0)
+                build_t<float>(*ix, (const float*)X, n, core, labels, s);
+            else
+                build_t<double>(*ix, (const double*)X, n, core, labels, s);
+            sync(s);   // the scratch is freed next
+        }
+        drop_scratch(*ix);
+    } catch (...) {
+        index_destroy(ix);
+        throw;
+    }
+    return ix;
+}
+
+void index_query(Index* ix, const void* Q, int dtype, int64_t m, int32_t* out, hipStream_t s) {
+    if (dtype != ix->dtype) throw Error(-1, "pd_index_query: the queries' dtype differs from the index's");
+    if (m >= 0xFFFFFFFFll) throw Error(-5, "pd_index_query: m must be < 2^32 - 1");
+    if (m == 0) return;
+    if (ix->dtype == 0)
+        query_t<float>(*ix, (const float*)Q, (uint64_t)m, out, s);
+    else
+        query_t<double>(*ix, (const double*)Q, (uint64_t)m, out, s);
+}
+
+void index_destroy(Index* ix) {
+    if (!ix) return;
+    (void)hipSetDevice(ix->device);
+    (void)hipDeviceSynchronize();   // a query may still read the buffers
+    ix->keep.release();
+    ix->work.arena.release();
+    if (ix->work.pinned) (void)hipHostFree(ix->work.pinned);
+    delete ix;
+}
+
+int index_device(const Index* ix) { return ix->device; }
+int64_t index_cores(const Index* ix) { return (int64_t)ix->nc; }
+
+}  // namespace pd

@@ -368,6 +368,17 @@ void halo_members(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int P,
                   const double* ebox_host, int64_t* counts_host, int64_t* members_dev,
                   int64_t members_cap, hipStream_t s);
 
+// Assignment index over the core points of a finished train (assign.hip):
+// owns its device memory and scratch, so it outlives any later train on the
+// context it was built beside.  X / core / labels / Q / out: device pointers.
+struct Index;
+Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const uint8_t* core,
+                   const int32_t* labels, double eps, int metric, hipStream_t s);
+void index_query(Index* ix, const void* Q, int dtype, int64_t m, int32_t* out, hipStream_t s);
+void index_destroy(Index* ix);
+int index_device(const Index* ix);
+int64_t index_cores(const Index* ix);
+
 // small helpers (api.hip)
 void sort_pairs_inplace(Ctx& ctx, void* keys, int key_bytes, uint32_t* vals, uint64_t n,
                         int key_bits, hipStream_t s);

@@ -292,7 +292,10 @@ class DBSCAN(object):
     :cluster_dict: kept for API parity; the reference never assigns it
 
     MI355X additions: ``labels_`` (device int32, input order),
-    ``core_sample_mask_`` (device uint8), ``n_clusters_``.
+    ``core_sample_mask_`` (device uint8), ``core_sample_indices_`` (device
+    int64, ascending), ``n_clusters_``; ``predict(points)`` assigns new
+    points to the trained clusters, ``fit_predict(data)`` is ``train`` then
+    ``labels_``.
 
     ``kd_sums``: KD moment summation.  'exact' (default): correctly rounded,
     order-independent double-double sums — the same boxes on one device or
@@ -344,6 +347,10 @@ class DBSCAN(object):
         self.n_clusters_ = None
         self.partitioner = None
         self.shard = None
+        self._points = None      # the training points (predict's index is built from them)
+        self._trained = None     # (eps, metric code) of the last train
+        self._index = None       # _native.Index, built by the first predict
+        self._group_trained = False
 
     def _process_group(self):
         """The process group of an opt-in sharded train: ``group=`` (a
@@ -372,7 +379,11 @@ class DBSCAN(object):
         if self.min_samples < 1:
             raise ValueError("min_samples must be >= 1")
         metric = _native.metric_code(self.metric)
+        self._drop_index()
+        self._points = None
+        self._trained = (float(self.eps), metric)
         group = self._process_group()
+        self._group_trained = group is not None
         if group is not None:
             return self._train_group(data, group, metric)
         if self.n_gpus is not None and int(self.n_gpus) > 1:
@@ -405,7 +416,66 @@ class DBSCAN(object):
         self.core_sample_mask_ = core
         self.n_clusters_ = ncl
         self.result = _Assignments(points, labels)
+        self._points = points
         return self
+
+    # ------------------------------------------------------------ assignment
+    def _drop_index(self):
+        index, self._index = self._index, None
+        if index is not None:
+            index.close()
+
+    @property
+    def core_sample_indices_(self):
+        """sklearn's attribute: indices of the core points, ascending (device
+        int64) — the core list of predict's index."""
+        if self.core_sample_mask_ is None:
+            return None
+        return torch.nonzero(self.core_sample_mask_).flatten()
+
+    def fit_predict(self, data):
+        """``train(data)``, then ``labels_`` (device int32, input order)."""
+        return self.train(data).labels_
+
+    def predict(self, data):
+        """
+        :param data: new points, in any form ``train`` takes
+        :return: device int32 tensor in the order of ``data``: for each point
+            the smallest label among the trained core points within ``eps``
+            of it, -1 if there is none
+
+        The distance test is the train's own (exact fp64 predicate) and the
+        minimum is its border rule, so ``predict(X_train)`` equals ``labels_``
+        — core, border and noise points — and the answer does not depend on
+        ``max_partitions`` or the order of the queries.  Queries are
+        converted to the dtype of the training points (float64 queries of a
+        float32 model are rounded to float32 first).  A NaN or infinite
+        coordinate raises, as in ``train``.
+
+        The device index over the core points (pd_index_build) is built by
+        the first call from the stored training points, ``core_sample_mask_``
+        and ``labels_``, kept on the model, and dropped by the next ``train``.
+        After an ``n_gpus=N`` train the points and labels are on one device
+        and this works as after a single-device train; after a ``group=``
+        train each rank holds only its slice, and predict raises.
+        """
+        if self.labels_ is None or self._trained is None:
+            raise ValueError("predict before train: the model has no clusters to assign to")
+        if self._group_trained:
+            raise ValueError("predict after a group= train is not supported: each rank holds "
+                             "only its slice of the points and labels (train with n_gpus=, or "
+                             "on one device, to predict)")
+        X = self._points.X
+        q = as_points(data, X.device).X
+        if q.shape[1] != X.shape[1]:
+            raise ValueError(f"predict: points have {q.shape[1]} coordinates, the model was "
+                             f"trained on {X.shape[1]}")
+        if q.dtype != X.dtype:
+            q = q.to(X.dtype)
+        if self._index is None:
+            eps, metric = self._trained
+            self._index = _native.Index(X, self.core_sample_mask_, self.labels_, eps, metric)
+        return self._index.query(q)
 
     # ------------------------------------------------------------ multi-GPU
     def _sharded_checks(self, points):
@@ -433,6 +503,7 @@ class DBSCAN(object):
             self.data = _PartitionRecords(self.neighbors, params)
         self.result = result
         self.shard = res
+        self._points = points
         return self
 
     def _train_group(self, data, group, metric):
