@@ -275,6 +275,44 @@ int32_t pd_train_tree(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int3
                       const double* boundary_host, const int32_t* newlab_host, int32_t* labels,
                       uint8_t* core, uint32_t* counts, int64_t* n_clusters, void* stream);
 
+/* ---- sample_weight (sklearn DBSCAN.fit(X, sample_weight=w)): a point is
+ * core when the weights of the points within eps of it, itself included, sum
+ * to min_samples or more.  weight: device, n fp64 values, weight[i] of point
+ * i, in place of the unweighted calls' `counts` output.  The sum is taken in
+ * fixed point, W_i = llrint(w_i * 2^20) (round half to even) as uint64, core
+ * iff sum W_j >= min_samples * 2^20: independent of the summation order and of
+ * P, and equal to sklearn's answer whenever every weight is a multiple of
+ * 2^-20 (otherwise it can differ only where sklearn's own float sum lies
+ * within k * 2^-21 of min_samples, k the number of neighbours).  A weight is
+ * valid iff it is finite and 0 <= w <= 2^31 (PD_EINVAL otherwise: a negative
+ * weight would let a partial neighbourhood out-sum the full one).  A
+ * zero-weight point adds nothing to others but can itself be core.  Labels
+ * follow the unweighted rules.  d <= 4, one device: d > 4 returns
+ * PD_EUNSUPPORTED, and the sharded train (pd_train_begin) takes no weights. */
+
+/* pd_cluster with sample weights. */
+int32_t pd_cluster_weighted(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                            double eps, int32_t min_samples, int32_t metric, int32_t* labels,
+                            uint8_t* core, const double* weight, int64_t* n_clusters_host,
+                            void* stream);
+
+/* pd_train with sample weights (every neighbourhood sums the weights of its
+ * own records; the merge is exact as before). */
+int32_t pd_train_weighted(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                          double eps, int32_t min_samples, int32_t metric, int32_t P,
+                          const double* ebox_host, const double* data_box_host,
+                          const int32_t* owner, int32_t* labels, uint8_t* core,
+                          const double* weight, int64_t* n_clusters_host, void* stream);
+
+/* pd_train_tree with sample weights. */
+int32_t pd_train_tree_weighted(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                               double eps, int32_t min_samples, int32_t metric, int32_t P,
+                               const double* ebox, const double* data_box, int32_t n_levels,
+                               const int32_t* level_sizes_host, const int32_t* cur_host,
+                               const int32_t* axis_host, const double* boundary_host,
+                               const int32_t* newlab_host, int32_t* labels, uint8_t* core,
+                               const double* weight, int64_t* n_clusters, void* stream);
+
 /* ---- sharded train (one process per device; the caller moves the buffers
  * between devices, e.g. torch.distributed over RCCL).  Replaces Spark's
  * partitionBy shuffle of the halo records (R:dbscan/dbscan.py:114-118) and the

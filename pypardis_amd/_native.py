@@ -60,7 +60,8 @@ EXPORTS = ["pd_abi_version", "pd_last_error", "pd_ctx_create", "pd_ctx_destroy",
            "pd_kdx_axes", "pd_kdx_counts", "pd_kdx_boundary", "pd_kdx_end", "pd_route2",
            "pd_pack2", "pd_results", "pd_results_scatter", "pd_comm_exchange", "pd_comm_abort",
            "pd_comm_self_check", "pd_comm_size", "pd_index_build", "pd_index_query",
-           "pd_index_destroy"]
+           "pd_index_destroy", "pd_cluster_weighted", "pd_train_weighted",
+           "pd_train_tree_weighted"]
 
 
 class PardisError(RuntimeError):
@@ -154,6 +155,11 @@ def load():
             "pd_index_build": ([P, P, I32, I64, I32, P, P, D, I32, ctypes.POINTER(P), P, P], I32),
             "pd_index_query": ([P, P, I32, I64, P, P], I32),
             "pd_index_destroy": ([P], I32),
+            "pd_cluster_weighted": ([P, P, I32, I64, I32, D, I32, I32, P, P, P, P, P], I32),
+            "pd_train_weighted": ([P, P, I32, I64, I32, D, I32, I32, I32, P, P, P, P, P, P, P, P],
+                                  I32),
+            "pd_train_tree_weighted": ([P, P, I32, I64, I32, D, I32, I32, I32, P, P, I32, P, P, P,
+                                        P, P, P, P, P, P, P], I32),
         }
         for name, (args, res) in sig.items():
             f = getattr(lib, name)
@@ -421,13 +427,44 @@ def halo_members(X, ebox, ctx=None):
     return counts, members[:total]
 
 
-def cluster(X, eps, min_samples, metric=PD_EUCLIDEAN, want_counts=False, ctx=None):
-    """sklearn fit_predict semantics on one point set (device tensors out)."""
+WEIGHT_MAX = 2.0 ** 31
+
+
+def _check_weight(sample_weight, X, want_counts):
+    """sample_weight of a train on X: a contiguous float64 device tensor of
+    one value per point (pd_*_weighted; their value check runs on the device)."""
+    w = sample_weight
+    if not isinstance(w, torch.Tensor) or not w.is_cuda or w.device != X.device:
+        raise TypeError("sample_weight must be a torch tensor on the device of X")
+    if w.dtype != torch.float64 or w.dim() != 1 or not w.is_contiguous():
+        raise TypeError("sample_weight must be a contiguous 1-D float64 tensor")
+    if w.shape[0] != X.shape[0]:
+        raise ValueError(f"sample_weight has {w.shape[0]} values for {X.shape[0]} points")
+    if X.shape[1] > 4:
+        raise ValueError("sample_weight is supported for d <= 4 only")
+    if want_counts:
+        raise ValueError("a weighted train returns no neighbour counts")
+    return w
+
+
+def cluster(X, eps, min_samples, metric=PD_EUCLIDEAN, want_counts=False, ctx=None,
+            sample_weight=None):
+    """sklearn fit_predict semantics on one point set (device tensors out).
+    sample_weight: float64 device tensor (n,), or None (pd_cluster_weighted)."""
     dt = _check_points(X)
+    if sample_weight is not None:
+        w = _check_weight(sample_weight, X, want_counts)
     ctx = ctx or context(X.device.index)
     n = X.shape[0]
     labels = torch.empty(n, dtype=torch.int32, device=X.device)
     core = torch.empty(n, dtype=torch.uint8, device=X.device)
+    if sample_weight is not None:
+        ncl = np.zeros(1, np.int64)
+        _check(load().pd_cluster_weighted(ctx.ptr, X.data_ptr(), dt, n, X.shape[1], float(eps),
+                                          int(min_samples), int(metric), labels.data_ptr(),
+                                          core.data_ptr(), w.data_ptr() if n else None,
+                                          ncl.ctypes.data, _stream(X.device)))
+        return labels, core, None, int(ncl[0])
     counts = torch.empty(n, dtype=torch.int32, device=X.device) if want_counts else None
     ncl = np.zeros(1, np.int64)
     _check(load().pd_cluster(ctx.ptr, X.data_ptr(), dt, n, X.shape[1], float(eps),
@@ -438,9 +475,12 @@ def cluster(X, eps, min_samples, metric=PD_EUCLIDEAN, want_counts=False, ctx=Non
 
 
 def train(X, eps, min_samples, metric, ebox, owner=None, data_box=None, want_counts=False,
-          out=None, ctx=None):
-    """The fused per-device pipeline (pd_train).  ebox: (P, 2, d) fp64."""
+          out=None, ctx=None, sample_weight=None):
+    """The fused per-device pipeline (pd_train).  ebox: (P, 2, d) fp64.
+    sample_weight: float64 device tensor (n,), or None (pd_train_weighted)."""
     dt = _check_points(X)
+    if sample_weight is not None:
+        w = _check_weight(sample_weight, X, want_counts)
     ctx = ctx or context(X.device.index)
     n, d = X.shape
     ebox = np.ascontiguousarray(ebox, np.float64)
@@ -455,6 +495,15 @@ def train(X, eps, min_samples, metric, ebox, owner=None, data_box=None, want_cou
     if data_box is not None:
         dbox = np.ascontiguousarray(data_box, np.float64).reshape(2 * d)
     ncl = np.zeros(1, np.int64)
+    if sample_weight is not None:
+        _check(load().pd_train_weighted(ctx.ptr, X.data_ptr(), dt, n, d, float(eps),
+                                        int(min_samples), int(metric), P, ebox.ctypes.data,
+                                        dbox.ctypes.data if dbox is not None else None,
+                                        owner.data_ptr() if owner is not None else None,
+                                        labels.data_ptr(), core.data_ptr(),
+                                        w.data_ptr() if n else None, ncl.ctypes.data,
+                                        _stream(X.device)))
+        return labels, core, None, int(ncl[0])
     _check(load().pd_train(ctx.ptr, X.data_ptr(), dt, n, d, float(eps), int(min_samples),
                            int(metric), P, ebox.ctypes.data,
                            dbox.ctypes.data if dbox is not None else None,
@@ -465,10 +514,13 @@ def train(X, eps, min_samples, metric, ebox, owner=None, data_box=None, want_cou
 
 
 def train_tree(X, eps, min_samples, metric, ebox, tree, data_box=None, want_counts=False,
-               ctx=None):
+               ctx=None, sample_weight=None):
     """pd_train_tree: pd_train with the KD split tree (sizes, cur, axis,
-    boundary, new) replayed per point instead of owner labels."""
+    boundary, new) replayed per point instead of owner labels.
+    sample_weight: float64 device tensor (n,), or None (pd_train_tree_weighted)."""
     dt = _check_points(X)
+    if sample_weight is not None:
+        w = _check_weight(sample_weight, X, want_counts)
     ctx = ctx or context(X.device.index)
     n, d = X.shape
     ebox = np.ascontiguousarray(ebox, np.float64)
@@ -482,6 +534,14 @@ def train_tree(X, eps, min_samples, metric, ebox, tree, data_box=None, want_coun
     counts = torch.empty(n, dtype=torch.int32, device=X.device) if want_counts else None
     dbox = None if data_box is None else np.ascontiguousarray(data_box, np.float64).reshape(2 * d)
     ncl = np.zeros(1, np.int64)
+    if sample_weight is not None:
+        _check(load().pd_train_tree_weighted(
+            ctx.ptr, X.data_ptr(), dt, n, d, float(eps), int(min_samples), int(metric),
+            ebox.shape[0], ebox.ctypes.data, dbox.ctypes.data if dbox is not None else None,
+            len(sizes), sizes.ctypes.data, cur.ctypes.data, axis.ctypes.data, bound.ctypes.data,
+            new.ctypes.data, labels.data_ptr(), core.data_ptr(), w.data_ptr() if n else None,
+            ncl.ctypes.data, _stream(X.device)))
+        return labels, core, None, int(ncl[0])
     _check(load().pd_train_tree(ctx.ptr, X.data_ptr(), dt, n, d, float(eps), int(min_samples),
                                 int(metric), ebox.shape[0], ebox.ctypes.data,
                                 dbox.ctypes.data if dbox is not None else None, len(sizes),

@@ -321,12 +321,15 @@ int32_t pd_halo_members(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, in
     });
 }
 
-int32_t pd_train(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d, double eps,
-                 int32_t min_samples, int32_t metric, int32_t P, const double* ebox,
-                 const double* data_box, const int32_t* owner, int32_t* labels, uint8_t* core,
-                 uint32_t* counts, int64_t* n_clusters, void* stream) {
+// pd_train / pd_train_weighted (weight: null = unweighted)
+static int32_t train_owner(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                           double eps, int32_t min_samples, int32_t metric, int32_t P,
+                           const double* ebox, const double* data_box, const int32_t* owner,
+                           int32_t* labels, uint8_t* core, uint32_t* counts, const double* weight,
+                           bool weighted, int64_t* n_clusters, void* stream) {
     return guard(ctx, [&] {
         check_common(ctx, X, n, d);
+        if (weighted && n > 0 && !weight) throw Error(PD_EINVAL, "null weight");
         if (!ebox) throw Error(PD_EINVAL, "null ebox");
         if (P > 1 && n > 0 && !owner) throw Error(PD_EINVAL, "owner labels required for P > 1");
         TrainArgs a;
@@ -344,20 +347,41 @@ int32_t pd_train(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d
         a.labels = labels;
         a.core = core;
         a.counts = counts;
+        a.weight = weight;
         a.stream = (hipStream_t)stream;
         train(ctx->c, a);
         if (n_clusters) *n_clusters = a.n_clusters;
     });
 }
 
-int32_t pd_train_tree(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d, double eps,
-                      int32_t min_samples, int32_t metric, int32_t P, const double* ebox,
-                      const double* data_box, int32_t n_levels, const int32_t* level_sizes,
-                      const int32_t* cur, const int32_t* axis, const double* boundary,
-                      const int32_t* newlab, int32_t* labels, uint8_t* core, uint32_t* counts,
-                      int64_t* n_clusters, void* stream) {
+int32_t pd_train(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d, double eps,
+                 int32_t min_samples, int32_t metric, int32_t P, const double* ebox,
+                 const double* data_box, const int32_t* owner, int32_t* labels, uint8_t* core,
+                 uint32_t* counts, int64_t* n_clusters, void* stream) {
+    return train_owner(ctx, X, dtype, n, d, eps, min_samples, metric, P, ebox, data_box, owner,
+                       labels, core, counts, nullptr, false, n_clusters, stream);
+}
+
+int32_t pd_train_weighted(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                          double eps, int32_t min_samples, int32_t metric, int32_t P,
+                          const double* ebox, const double* data_box, const int32_t* owner,
+                          int32_t* labels, uint8_t* core, const double* weight,
+                          int64_t* n_clusters, void* stream) {
+    return train_owner(ctx, X, dtype, n, d, eps, min_samples, metric, P, ebox, data_box, owner,
+                       labels, core, nullptr, weight, true, n_clusters, stream);
+}
+
+// pd_train_tree / pd_train_tree_weighted
+static int32_t train_tree(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                          double eps, int32_t min_samples, int32_t metric, int32_t P,
+                          const double* ebox, const double* data_box, int32_t n_levels,
+                          const int32_t* level_sizes, const int32_t* cur, const int32_t* axis,
+                          const double* boundary, const int32_t* newlab, int32_t* labels,
+                          uint8_t* core, uint32_t* counts, const double* weight, bool weighted,
+                          int64_t* n_clusters, void* stream) {
     return guard(ctx, [&] {
         check_common(ctx, X, n, d);
+        if (weighted && n > 0 && !weight) throw Error(PD_EINVAL, "null weight");
         if (!ebox) throw Error(PD_EINVAL, "null ebox");
         if (d > kMaxDim) throw Error(PD_EUNSUPPORTED, "pd_train_tree: d > 4 (use pd_train)");
         if (n_levels < 0 || n_levels > 16 ||
@@ -384,17 +408,47 @@ int32_t pd_train_tree(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int3
         a.labels = labels;
         a.core = core;
         a.counts = counts;
+        a.weight = weight;
         a.stream = (hipStream_t)stream;
         train(ctx->c, a);
         if (n_clusters) *n_clusters = a.n_clusters;
     });
 }
 
-int32_t pd_cluster(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d, double eps,
-                   int32_t min_samples, int32_t metric, int32_t* labels, uint8_t* core,
-                   uint32_t* counts, int64_t* n_clusters, void* stream) {
+int32_t pd_train_tree(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d, double eps,
+                      int32_t min_samples, int32_t metric, int32_t P, const double* ebox,
+                      const double* data_box, int32_t n_levels, const int32_t* level_sizes,
+                      const int32_t* cur, const int32_t* axis, const double* boundary,
+                      const int32_t* newlab, int32_t* labels, uint8_t* core, uint32_t* counts,
+                      int64_t* n_clusters, void* stream) {
+    return train_tree(ctx, X, dtype, n, d, eps, min_samples, metric, P, ebox, data_box, n_levels,
+                      level_sizes, cur, axis, boundary, newlab, labels, core, counts, nullptr,
+                      false, n_clusters, stream);
+}
+
+int32_t pd_train_tree_weighted(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                               double eps, int32_t min_samples, int32_t metric, int32_t P,
+                               const double* ebox, const double* data_box, int32_t n_levels,
+                               const int32_t* level_sizes, const int32_t* cur,
+                               const int32_t* axis, const double* boundary,
+                               const int32_t* newlab, int32_t* labels, uint8_t* core,
+                               const double* weight, int64_t* n_clusters, void* stream) {
+    return train_tree(ctx, X, dtype, n, d, eps, min_samples, metric, P, ebox, data_box, n_levels,
+                      level_sizes, cur, axis, boundary, newlab, labels, core, nullptr, weight,
+                      true, n_clusters, stream);
+}
+
+// pd_cluster / pd_cluster_weighted
+static int32_t cluster_one(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                           double eps, int32_t min_samples, int32_t metric, int32_t* labels,
+                           uint8_t* core, uint32_t* counts, const double* weight, bool weighted,
+                           int64_t* n_clusters, void* stream) {
     return guard(ctx, [&] {
         check_common(ctx, X, n, d);
+        if (weighted && n > 0 && !weight) throw Error(PD_EINVAL, "null weight");
+        if (weighted && d > kMaxDim)
+            throw Error(PD_EUNSUPPORTED, "sample_weight: supported for d <= 4 only (the dense "
+                                         "d > 4 path counts neighbours unweighted)");
         TrainArgs a;
         a.X = X;
         a.dtype = dtype;
@@ -407,6 +461,7 @@ int32_t pd_cluster(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t
         a.labels = labels;
         a.core = core;
         a.counts = counts;
+        a.weight = weight;
         a.stream = (hipStream_t)stream;
         std::vector<double> box(2 * (size_t)d, 0.0);
         if (n > 0) {
@@ -419,6 +474,21 @@ int32_t pd_cluster(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t
         train(ctx->c, a);
         if (n_clusters) *n_clusters = a.n_clusters;
     });
+}
+
+int32_t pd_cluster(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d, double eps,
+                   int32_t min_samples, int32_t metric, int32_t* labels, uint8_t* core,
+                   uint32_t* counts, int64_t* n_clusters, void* stream) {
+    return cluster_one(ctx, X, dtype, n, d, eps, min_samples, metric, labels, core, counts,
+                       nullptr, false, n_clusters, stream);
+}
+
+int32_t pd_cluster_weighted(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
+                            double eps, int32_t min_samples, int32_t metric, int32_t* labels,
+                            uint8_t* core, const double* weight, int64_t* n_clusters,
+                            void* stream) {
+    return cluster_one(ctx, X, dtype, n, d, eps, min_samples, metric, labels, core, nullptr,
+                       weight, true, n_clusters, stream);
 }
 
 // ---------------------------------------------------------------- sharded train

@@ -846,6 +846,38 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const T* __restrict__ X,
     wave_append(dup_list, dup_count, r < R && (v & kDupBit), (uint32_t)r);
 }
 
+// sample_weight (pd_*_weighted): the fp64 weights as unsigned fixed point,
+// W = llrint(w * 2^20) (round half to even; the product is exact, a power of
+// two), so that a neighbourhood's weight sum is an integer sum — the same in
+// any order, and never smaller for a superset (the merge argument, DESIGN.md
+// §2).  Valid: finite, 0 <= w <= 2^31 (W <= 2^51); the invalid ones are
+// counted (one atomic per wave) and stored as 0.
+constexpr int kWeightFrac = 20;
+constexpr double kWeightMax = 2147483648.0;
+__global__ __launch_bounds__(kBlock) void weight_fix_kernel(const double* __restrict__ w, uint64_t n,
+                                                            uint64_t* __restrict__ W,
+                                                            uint32_t* __restrict__ bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const double x = i < n ? w[i] : 0.0;
+    const bool ok = x >= 0.0 && x <= kWeightMax;   // (NaN fails both)
+    if (i < n) W[i] = ok ? (uint64_t)llrint(x * (double)(1ull << kWeightFrac)) : 0ull;
+    const unsigned long long b = __ballot(!ok);
+    if (b && (threadIdx.x & 63) == __ffsll(b) - 1) atomicAdd(bad, (uint32_t)__popcll(b));
+}
+
+// The fixed-point weight of each record, in record (key) order: the weighted
+// count sweep loads it beside the candidate's row.
+__global__ __launch_bounds__(kBlock) void record_weight_kernel(const uint64_t* __restrict__ W,
+                                                               const uint32_t* __restrict__ vals,
+                                                               uint64_t R, uint64_t n,
+                                                               uint64_t* __restrict__ wrec) {
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= R) return;
+    const uint64_t i = vals[r] & kIdMask;
+    if (!PD_OK(i < n, 8, i)) return;
+    wrec[r] = W[i];
+}
+
 template <typename K>
 __global__ void part_start_kernel(const K* __restrict__ keys, uint64_t R,
                                   const PartGrid* __restrict__ parts, int P,
@@ -1716,12 +1748,22 @@ constexpr int kCountWpe = PD_COUNT_WPE, kBorderWpe = PD_BORDER_WPE;   // (A/B bu
 // (record, directory words, cell starts, candidates) stays in L2, at full
 // occupancy and steady state: the sweep's latency ceiling
 // (tools/count_ceiling.py).  Replicas write the same values.
-template <typename T, int D, int M, bool ST, int WPE = 1, bool REPLAY = false>
+// WT (sample_weight): a record is core when the fixed-point weights of its
+// hits (wrec, record order; self included) sum to wthr = min_samples << 20 or
+// more.  The four weights of a round trip are loaded with the rows, before
+// the predicates; the sum is a uint64 (below 2^51 before a step, which adds
+// at most 4 weights of at most 2^51: no overflow), and the sweep stops once
+// it reaches wthr.  Weights are non-negative, so a record that ends below
+// wthr never stopped early: its cnt and two smallest hits are complete, and
+// the flag bits 2 and 4 keep their cardinality meaning.  Every unweighted
+// instantiation compiles exactly as before (if constexpr).
+template <typename T, int D, int M, bool ST, int WPE = 1, bool REPLAY = false, bool WT = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE))) void count4_kernel(
     const T* __restrict__ Xs, uint32_t R, Cells C, double eps, double eps2, float lo, float hi,
     uint32_t ms, int full, uint32_t rot_min, uint8_t* __restrict__ core,
     uint32_t* __restrict__ mn_out, uint32_t* __restrict__ cnt_out,
-    unsigned long long* __restrict__ stats, uint32_t rmod) {
+    unsigned long long* __restrict__ stats, uint32_t rmod,
+    const uint64_t* __restrict__ wrec = nullptr, uint64_t wthr = 0) {
     constexpr int NR = NRows<D>::v;
     constexpr int B = NR < 3 ? NR : 3, NB = NR / B;
     uint32_t r = rec_index();
@@ -1735,6 +1777,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE))) v
     float e2 = M == 0 ? (float)eps2 : (float)eps;
     e2 = e2 * (1.0f + 1.0f / 65536.0f);
     uint32_t cnt = 0, mn = kNone, mn2 = kNone, n_cand = 0;
+    uint64_t wsum = 0;
+    const uint64_t wstop = full ? ~0ull : wthr;
+    (void)wsum;
+    (void)wstop;
     with_part(C.part_start, C.P, r, [&](int L, auto U) {
         Count3Grid<T, D, M, decltype(U)::value> g;
         g.load(C.parts + L);
@@ -1763,6 +1809,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE))) v
                 for (uint32_t v = 0; v < tot; v += 4) {
                     uint32_t j[4];
                     T b[4][D];
+                    uint64_t wb[4];
+                    (void)wb;
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         uint32_t w = v + u;
@@ -1772,17 +1820,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE))) v
                         }
                         j[u] = jpos(w);
                         load_raw<T, D>(Xs, v + u < tot ? j[u] : r, b[u]);
+                        if constexpr (WT) wb[u] = wrec[v + u < tot ? j[u] : r];
                     }
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const bool h = (v + u < tot) && pr(b[u]);
                         cnt += h ? 1u : 0u;
+                        if constexpr (WT) wsum += h ? wb[u] : 0ull;
                         const uint32_t x = h ? j[u] : kNone;
                         mn2 = min(mn2, max(mn, x));   // the two smallest hits
                         mn = min(mn, x);
                     }
                     if constexpr (ST) n_cand += (tot - v < 4u ? tot - v : 4u);
-                    if (cnt >= stop) return true;
+                    if constexpr (WT) {
+                        if (wsum >= wstop) return true;
+                    } else {
+                        if (cnt >= stop) return true;
+                    }
                 }
                 return false;
             };
@@ -1793,9 +1847,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE))) v
     // bit 2: exactly one neighbour besides the record itself (no early exit
     // below min_samples, so the sweep saw it, and it is the other of the two
     // smallest hits): owner_kernel attaches such a border record directly
-    core[r] = (cnt >= ms ? 1 : 0) | (cnt >= 2 ? 2 : 0) | (cnt == 2 ? 4 : 0);
+    const bool is_core = WT ? wsum >= wthr : cnt >= ms;
+    core[r] = (is_core ? 1 : 0) | (cnt >= 2 ? 2 : 0) | (cnt == 2 ? 4 : 0);
     reinterpret_cast<uint2*>(mn_out)[r] = make_uint2(mn, mn2);
-    if (cnt_out) cnt_out[r] = full ? cnt : (cnt < ms ? cnt : ms);
+    if constexpr (!WT)
+        if (cnt_out) cnt_out[r] = full ? cnt : (cnt < ms ? cnt : ms);
     if constexpr (ST) atomicAdd(stats + 0, (unsigned long long)n_cand);
 }
 
@@ -2765,6 +2821,28 @@ void launch_count(hipStream_t s, const T* Xs, uint32_t R, const Cells& C, double
                            Xs, R, C, eps, eps2, lo, hi, ms, full, rot_min, core, mn, cnt, st, 0u);
 }
 
+// The weighted sweep (sample_weight): wrec = the records' fixed-point
+// weights, wthr = min_samples << 20.  Its waves per SIMD are the most at which
+// the four 64-bit weights in flight and the sum still leave the kernel
+// without scratch (kernel-resource-usage remarks): d <= 2: 8 (46 VGPRs),
+// d = 3: 6 (80 VGPRs), d = 4: 5 (92-94 VGPRs).  At 8 the d = 3 kernel spills
+// 60-64 B per lane and the d = 4 one 104-140 B; DESIGN.md §11 has the A/B on
+// C2 (d = 3), 6 against 8.  (A/B builds: -DPD_WCOUNT_WPE=N for every d.)
+#ifndef PD_WCOUNT_WPE
+#define PD_WCOUNT_WPE 0
+#endif
+template <int D>
+constexpr int kWCountWpe = PD_WCOUNT_WPE ? PD_WCOUNT_WPE : (D <= 2 ? 8 : (D == 3 ? 6 : 5));
+template <typename T, int D, int M>
+void launch_count_weighted(hipStream_t s, const T* Xs, uint32_t R, const Cells& C, double eps,
+                           double eps2, float lo, float hi, uint32_t ms, int full,
+                           uint32_t rot_min, uint8_t* core, uint32_t* mn, const uint64_t* wrec) {
+    hipLaunchKernelGGL((count4_kernel<T, D, M, false, kWCountWpe<D>, false, true>), dim3(blocks(R)),
+                       dim3(kBlock), 0, s, Xs, R, C, eps, eps2, lo, hi, ms, full, rot_min, core, mn,
+                       (uint32_t*)nullptr, (unsigned long long*)nullptr, 0u, wrec,
+                       (uint64_t)ms << kWeightFrac);
+}
+
 // PD_OPT_COUNT_REPLAY (measurement): the shipped count sweep over `reps`
 // replicas of the R records (lane i sweeps record i % R), timed with its own
 // events into PD_T_COUNT_KERNEL.
@@ -3058,6 +3136,23 @@ void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t
     tm.mark();   // 2
     hipLaunchKernelGGL((gather_kernel<T, D>), dim3(blocks(R)), dim3(kBlock), 0, s, X, (uint64_t)R,
                        vals, Xs, dup_list, lcount, rep);
+    // sample_weight: the fixed-point weights (their validity count is read
+    // back at the cell-count sync below), then each record's weight
+    uint64_t* wrec = nullptr;
+    uint32_t* wbad = nullptr;
+    if (a.weight) {
+        uint64_t* wfix = ctx.arena.get<uint64_t>("weight_fix", n);
+        wrec = ctx.arena.get<uint64_t>("weight_rec", R);
+        wbad = ctx.arena.get<uint32_t>("weight_bad", 4);
+        PD_HIP(hipMemsetAsync(wbad, 0, sizeof(uint32_t), s));
+        hipLaunchKernelGGL(weight_fix_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, a.weight, n, wfix,
+                           wbad);
+        if (R)
+            hipLaunchKernelGGL(record_weight_kernel, dim3(blocks(R)), dim3(kBlock), 0, s, wfix, vals,
+                               (uint64_t)R, n, wrec);
+        PD_HIP(hipGetLastError());
+        check_bounds(s, "record_weight_kernel");
+    }
     tm.mark();   // 3
 
     // ---- cell directory
@@ -3090,10 +3185,25 @@ void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t
     if (R) {
         uint32_t* hnc = (uint32_t*)((char*)pinned(ctx, 16) + 8);
         PD_HIP(hipMemcpyAsync(hnc, dncells, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        // (sample_weight: the invalid-weight count rides on this sync)
+        uint32_t* hwb = hnc + 1;
+        if (wbad) PD_HIP(hipMemcpyAsync(hwb, wbad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         sync(s);
         cgrid0 = std::max<uint64_t>(1, std::min<uint64_t>(*hnc, R));
+        if (wbad && *hwb)
+            throw Error(-1, "sample_weight: " + std::to_string(*hwb) +
+                                " value(s) not finite or outside [0, 2^31]");
+        wbad = nullptr;
     }
 #endif
+    if (wbad) {   // (no cell-count sync in this build / an empty record set)
+        uint32_t* hwb = (uint32_t*)pinned(ctx, sizeof(uint32_t));
+        PD_HIP(hipMemcpyAsync(hwb, wbad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        sync(s);
+        if (*hwb)
+            throw Error(-1, "sample_weight: " + std::to_string(*hwb) +
+                                " value(s) not finite or outside [0, 2^31]");
+    }
     // per-tile popcount prefix over a uint4 array's (x, y) bits into .z
     auto prefix_words = [&](uint4* d, uint64_t nw, bool read_total) -> uint64_t {
         const unsigned wtiles = (unsigned)std::max<uint64_t>(1, (nw + 4 * kBlock - 1) / (4 * kBlock));
@@ -3192,13 +3302,16 @@ void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t
     }
     if (R) {
         const uint32_t rot = ctx.count_rotate ? (uint32_t)ctx.count_rotate : 0xFFFFFFFFu;
-        if (sst)
+        if (wrec)
+            launch_count_weighted<T, D, M>(s, Xs, R, C, eps, eps2, slo, shi, (uint32_t)a.min_samples,
+                                           ctx.full_counts ? 1 : 0, rot, core, mn, wrec);
+        else if (sst)
             launch_count<T, D, M, true>(s, Xs, R, C, eps, eps2, slo, shi, (uint32_t)a.min_samples,
                                         ctx.full_counts ? 1 : 0, rot, core, mn, cnt_rec, sst);
         else
             launch_count<T, D, M, false>(s, Xs, R, C, eps, eps2, slo, shi, (uint32_t)a.min_samples,
                                          ctx.full_counts ? 1 : 0, rot, core, mn, cnt_rec, sst);
-        if (ctx.count_replay > 0 && !sst)
+        if (ctx.count_replay > 0 && !sst && !wrec)
             ctx.t.count_kernel = replay_count<T, D, M>(
                 s, Xs, R, (uint32_t)ctx.count_replay, C, eps, eps2, slo, shi,
                 (uint32_t)a.min_samples, ctx.full_counts ? 1 : 0, rot, core, mn, cnt_rec);
@@ -3734,6 +3847,16 @@ void train(Ctx& ctx, TrainArgs& a) {
     if (a.P < 1) throw Error(-1, "need at least one neighbourhood");
     if (a.n > (int64_t)kIdMask) throw Error(-5, "n must be < 2^30 points per device");
     if (a.phase == 0 && !a.labels && a.n) throw Error(-1, "labels output is required");
+    if (a.weight) {
+        // (the dense count pass tallies pairs without the row
+        // index in hand; the sharded path would carry the weight in the halo
+        // exchange)
+        if (a.phase != 0)
+            throw Error(-5, "sample_weight: the sharded train (pd_train_begin) does not take weights");
+        if (a.d > kMaxDim)
+            throw Error(-5, "sample_weight: supported for d <= 4 only (the dense d > 4 path "
+                            "counts neighbours unweighted)");
+    }
     ctx.t = Timings{};
     if (a.d > kMaxDim) {
         // dense tiles (dense.hip): one pass over all points; the halo + merge

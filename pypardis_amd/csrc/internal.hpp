@@ -211,6 +211,10 @@ struct TrainArgs {
     int32_t* labels = nullptr;        // device out, n
     uint8_t* core = nullptr;          // device out, n (nullable)
     uint32_t* counts = nullptr;       // device out, n (nullable; owner-record counts)
+    // device, n fp64 sample weights (null: unweighted).  Phase 0, d <= 4 only:
+    // a point is core when the weights within eps of it (fixed point, 2^-20
+    // units) sum to min_samples or more
+    const double* weight = nullptr;
     int64_t n_clusters = 0;           // out
     hipStream_t stream = nullptr;
     // sharded (multi-device) train: phase 1 = local clustering + exports,

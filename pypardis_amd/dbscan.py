@@ -111,29 +111,36 @@ class _Neighborhoods(dict):
         return iter(self.items())
 
 
-def _partition_records(X, keys, n_parts, members, cluster, params):
+def _partition_records(X, keys, n_parts, members, cluster, params, weight=None):
     """The reference's per-partition records (R:dbscan/dbscan.py:116-125 with
     dbscan_partition, :12-34): for each neighbourhood L (partitionBy order)
     and each of its points in input order, ``(key, 'L:c')`` or ``(key,
     'L:c*')`` — c the neighbourhood's own sklearn label of the point, '*' a
     non-core point.  members(L) -> ascending point indices of neighbourhood
-    L; cluster(X_L, eps, min_samples, metric) -> (labels, core) numpy."""
+    L; cluster(X_L, eps, min_samples, metric) -> (labels, core) numpy.
+    weight (device fp64, one per point): each neighbourhood is clustered with
+    its own points' weights, cluster(..., sample_weight=w_L)."""
     recs = []
     metric = _native.metric_code(params.get('metric', 'euclidean'))
     for L in range(n_parts):
         idx = np.asarray(members(L), np.int64)
         if not len(idx):
             continue
-        XL = X[torch.from_numpy(idx).to(X.device)].contiguous()
-        lab, core = cluster(XL, params['eps'], params['min_samples'], metric)
+        sel = torch.from_numpy(idx).to(X.device)
+        XL = X[sel].contiguous()
+        if weight is None:
+            lab, core = cluster(XL, params['eps'], params['min_samples'], metric)
+        else:
+            lab, core = cluster(XL, params['eps'], params['min_samples'], metric,
+                                sample_weight=weight[sel].contiguous())
         recs.extend((k, '%i:%i%s' % (L, c, '' if f else '*'))
                     for k, c, f in zip(keys[idx].tolist(), np.asarray(lab).tolist(),
                                        np.asarray(core).tolist()))
     return recs
 
 
-def _device_cluster(X, eps, min_samples, metric):
-    lab, core, _, _ = _native.cluster(X, eps, min_samples, metric)
+def _device_cluster(X, eps, min_samples, metric, sample_weight=None):
+    lab, core, _, _ = _native.cluster(X, eps, min_samples, metric, sample_weight=sample_weight)
     return lab.cpu().numpy(), core.cpu().numpy()
 
 
@@ -141,11 +148,13 @@ class _PartitionRecords(object):
     """``DBSCAN.data`` after ``train`` (R:dbscan/dbscan.py:116-125): the
     records of the per-partition clustering (_partition_records).  Built
     lazily on first use, one pd_cluster per neighbourhood; the global labels
-    never depend on it."""
+    never depend on it.  After a weighted train each neighbourhood is
+    clustered with its points' weights (pd_cluster_weighted)."""
 
-    def __init__(self, neighbors, params):
+    def __init__(self, neighbors, params, weight=None):
         self.neighbors = neighbors
         self.params = params
+        self.weight = weight
         self._recs = None
 
     def _build(self):
@@ -153,7 +162,7 @@ class _PartitionRecords(object):
             nb = self.neighbors
             self._recs = _partition_records(nb.points.X, nb.points.key_array(), len(nb),
                                             lambda L: nb[L].indices(), _device_cluster,
-                                            self.params)
+                                            self.params, self.weight)
         return self._recs
 
     def collect(self):
@@ -297,6 +306,23 @@ class DBSCAN(object):
     points to the trained clusters, ``fit_predict(data)`` is ``train`` then
     ``labels_``.
 
+    ``sample_weight`` (``train`` / ``fit_predict``; sklearn's ``fit``
+    argument): one weight per point; a point is core when the weights of the
+    points within ``eps`` of it, itself included, sum to ``min_samples`` or
+    more — e.g. multiplicities of deduplicated data.  The sum is taken in
+    fixed point, ``W = llrint(w * 2**20)`` (round half to even), core iff
+    ``sum W >= min_samples * 2**20``: it does not depend on the order of
+    summation or on ``max_partitions``, and equals sklearn's answer exactly
+    whenever every weight is a multiple of 2**-20 (integers, dyadic
+    fractions); for other weights the core flag can differ from sklearn's
+    only where sklearn's own float sum lies within k * 2**-21 of
+    ``min_samples`` (k neighbours).  A zero-weight point adds nothing to
+    others but can itself be core.  Limits: weights must be finite and in
+    [0, 2**31] — negative weights raise (sklearn allows them, but a partial
+    neighbourhood could then out-sum the full one, which the halo merge and
+    the sweep's early exit rely on never happening); d <= 4; one device (no
+    ``group=``, no ``n_gpus`` > 1).
+
     ``kd_sums``: KD moment summation.  'exact' (default): correctly rounded,
     order-independent double-double sums — the same boxes on one device or
     many; 'sequential': the reference's left-to-right fold, bit-identical to
@@ -369,9 +395,29 @@ class DBSCAN(object):
                              f"{dist.get_world_size(group)} ranks")
         return group
 
-    def train(self, data):
+    def _weights(self, sample_weight, points):
+        """sample_weight as a float64 tensor on the points' device, one value
+        per point (the range check runs on the device, inside the train)."""
+        w = sample_weight
+        if isinstance(w, torch.Tensor):
+            w = w.detach()
+        else:
+            w = torch.from_numpy(np.ascontiguousarray(np.asarray(w, dtype=np.float64)))
+        if w.dim() != 1 or w.shape[0] != points.n:
+            raise ValueError(f"sample_weight must hold one value per point: got shape "
+                             f"{tuple(w.shape)} for {points.n} points")
+        if points.d > 4:
+            raise ValueError("sample_weight is supported for d <= 4 only (the dense d > 4 "
+                             "path counts neighbours unweighted)")
+        return w.to(device=points.X.device, dtype=torch.float64).contiguous()
+
+    def train(self, data, sample_weight=None):
         """
         :param data: RDD-like / iterable of (key, vector), or (n, d) array/tensor
+        :param sample_weight: None, or one weight per point of ``data`` in the
+            order given (array, list or tensor; finite, 0 <= w <= 2**31): a
+            point is core when the weights within ``eps`` of it sum to
+            ``min_samples`` or more (class docstring).  Single device, d <= 4.
         Train the model (R:dbscan/dbscan.py:104-126).
         """
         if not (self.eps > 0):
@@ -379,6 +425,11 @@ class DBSCAN(object):
         if self.min_samples < 1:
             raise ValueError("min_samples must be >= 1")
         metric = _native.metric_code(self.metric)
+        if sample_weight is not None:
+            if self.group is not None:
+                raise ValueError("sample_weight is single-device: not supported with group=")
+            if self.n_gpus is not None and int(self.n_gpus) > 1:
+                raise ValueError("sample_weight is single-device: not supported with n_gpus > 1")
         self._drop_index()
         self._points = None
         self._trained = (float(self.eps), metric)
@@ -389,6 +440,7 @@ class DBSCAN(object):
         if self.n_gpus is not None and int(self.n_gpus) > 1:
             return self._train_devices(data, metric)
         points = as_points(data, self.device)
+        weight = None if sample_weight is None else self._weights(sample_weight, points)
         parts = KDPartitioner(points, self.max_partitions, sums=self.kd_sums)
         self.partitioner = parts
         self.bounding_boxes = parts.bounding_boxes
@@ -400,18 +452,28 @@ class DBSCAN(object):
         # the reference's self.data after train: the per-partition records
         self.data = _PartitionRecords(self.neighbors, {'eps': self.eps,
                                                        'min_samples': self.min_samples,
-                                                       'metric': self.metric})
+                                                       'metric': self.metric}, weight)
         lo, hi = parts.data_box
         tree = parts.split_tree() if len(ebox) > 1 and points.d <= 4 else None
-        if tree is not None:
-            # the owner of each point is found by replaying the KD splits in
-            # the halo pass (no owner array, no final split pass)
-            labels, core, _, ncl = _native.train_tree(points.X, self.eps, self.min_samples, metric,
-                                                      ebox, tree, data_box=np.stack([lo, hi]))
-        else:
-            owner = parts.labels if len(ebox) > 1 else None
-            labels, core, _, ncl = _native.train(points.X, self.eps, self.min_samples, metric,
-                                                 ebox, owner=owner, data_box=np.stack([lo, hi]))
+        try:
+            if tree is not None:
+                # the owner of each point is found by replaying the KD splits in
+                # the halo pass (no owner array, no final split pass)
+                labels, core, _, ncl = _native.train_tree(points.X, self.eps, self.min_samples,
+                                                          metric, ebox, tree,
+                                                          data_box=np.stack([lo, hi]),
+                                                          sample_weight=weight)
+            else:
+                owner = parts.labels if len(ebox) > 1 else None
+                labels, core, _, ncl = _native.train(points.X, self.eps, self.min_samples, metric,
+                                                     ebox, owner=owner,
+                                                     data_box=np.stack([lo, hi]),
+                                                     sample_weight=weight)
+        except _native.PardisError as e:
+            # (an invalid weight is found on the device: sklearn's ValueError)
+            if weight is not None and e.code == _native.PD_EINVAL and "sample_weight" in str(e):
+                raise ValueError(str(e)) from None
+            raise
         self.labels_ = labels
         self.core_sample_mask_ = core
         self.n_clusters_ = ncl
@@ -433,9 +495,10 @@ class DBSCAN(object):
             return None
         return torch.nonzero(self.core_sample_mask_).flatten()
 
-    def fit_predict(self, data):
-        """``train(data)``, then ``labels_`` (device int32, input order)."""
-        return self.train(data).labels_
+    def fit_predict(self, data, sample_weight=None):
+        """``train(data, sample_weight)``, then ``labels_`` (device int32,
+        input order)."""
+        return self.train(data, sample_weight).labels_
 
     def predict(self, data):
         """
