@@ -8,10 +8,19 @@
 //
 // with <.,.> from split-bf16 MFMA (x = hi + lo, hi = bf16(x), lo = bf16(x -
 // hi); hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16, fp32 accumulation)
-// and a rigorous error band |d2~ - d2| <= c (|x_i|^2 + |x_j|^2), c = 2^-13:
-// the split drops <= 3 * 2^-18 |x||y|, the fp32 accumulation over K <= 128
-// adds <= 2^-17 |x||y|, fp32 rounding of the coordinates and of d2~ itself
-// < 2^-21 (|x|^2 + |y|^2), and 2|x||y| <= |x|^2 + |y|^2 — a > 4x margin.
+// and a rigorous error band |d2~ - d2| <= c (|x_i|^2 + |x_j|^2), c = 2^-13.
+// With s = |x|^2 + |y|^2 (so 2|x||y| <= s): a bf16 keeps 8 significant bits,
+// so |x - hi| <= 2^-8 |x| (reached just above a power of two) and the
+// residual r = x - hi - lo has |r| <= 2^-8 |x - hi| <= 2^-16 |x|, per
+// coordinate.  The split drops lo.lo' + r.y + (hi + lo).r' <= 3.01 * 2^-16
+// |x||y| of the dot product, i.e. <= 3.01 * 2^-16 s = 4.6e-5 s of d2 (met to
+// half when every coordinate rounds the same way: shell_pairs(mantissa=
+// "bf16") in tests/dense_adversarial.py measures 2.2e-5 s; random mantissas
+// stay below 2^-17 s).  The fp32 accumulation — at worst one rounding per
+// product, 3 * 128 of them, each <= 2^-24 of a partial sum <= |x|^2 / 2 +
+// |y|^2 — adds <= 4.6e-5 s to d2; fp32 rounding of the coordinates and of
+// d2~ itself < 2^-21 s.  In all <= 9.3e-5 s against c = 1.22e-4: a 1.3x
+// margin in the worst case of everything at once.
 // Pairs outside the band are decided exactly by the bound; pairs inside it
 // are re-tested with sklearn's kd_tree leaf predicate (fp64, per axis in
 // order, no FMA; SK:metrics/_dist_metrics.pxd.tp:39-49).  So counts, core
@@ -56,11 +65,19 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));   // 32 e4m3 values
 enum { kCount = 0, kLink = 1, kBorder = 2 };
 constexpr int kTile = 64;                 // points per wave tile (2 MFMA tiles of 32)
 constexpr float kBandC = 1.0f / 8192.0f;  // error band c (see header)
-// Count pass screen: hi.hi alone (one MFMA per k-step instead of three) is
-// within 2^-8 (1 + 2^-10) |x||y| + 2^-17 s of the dot product (bf16 rounds
-// each coordinate by <= 2^-9 of itself; products exact, fp32 accumulation
-// over <= 128 terms), i.e. d2 within 2^-8 * 1.01 s.  A tile where no pair
-// passes the band c' = 2^-7 holds no neighbour (a 1.9x margin), so only
+// Count pass screen: hi.hi alone (one MFMA per k-step instead of three).
+// bf16 rounds each coordinate by <= u = 2^-8 / (1 + 2^-8) of itself (at a
+// mantissa of 1 + 2^-8), so hi.hi is within (2u + u^2) |x||y| = 0.0077973
+// |x||y| of the dot product and d2 within 0.0077973 s (products exact).  The
+// fp32 accumulation of <= 128 products, each rounding <= 2^-24 of a partial
+// sum <= |x_i|^2 / 2 + |x_j|^2, moves the accumulator by <= 3.8e-6 |x_i|^2 +
+// 7.6e-6 |x_j|^2.  The screen keeps a pair when acc_hh - ta_j >= bc (below);
+// for a pair with d2 <= ehi the left side exceeds the right by at least
+// ((c' - 0.0077973) |x_i|^2 + (1.001 c' - 0.0077973) |x_j|^2) / 2 = 7.6e-6
+// |x_i|^2 + 1.16e-5 |x_j|^2 before rounding (max_j |x_j|^2 >= |x_j|^2): c' =
+// 2^-7 covers the formats' worst case with 0.2 % to spare and the rounding
+// with 1.5x.  (shell_pairs(mantissa="bf16") comes within 2 % of that worst
+// case.)  A tile where no pair passes the screen holds no neighbour, so only
 // tiles that can hold one fetch the lo fragments and finish the split
 // product; C3 pairs lie ~100 eps^2 apart, so most tiles stop at the screen.
 constexpr float kScreenC = 1.0f / 128.0f;
