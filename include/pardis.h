@@ -124,39 +124,20 @@ enum pd_option {
                                 Same records either way */,
     PD_OPT_HALO_CAP = 26      /* single-pass halo record capacity (tests: force the overflow
                                 path); 0 (default): n + n/8 + 4096 */,
-    PD_OPT_KD_FUSE = 27       /* device-decided KD (pd_kd_build): 0 (default) a moments pass and
-                                a counts pass per level; 1: a level of <= 2 splits counts its
-                                candidates and sums the moments of each (split, candidate
-                                interval) in one pass, so the next level's moments need no pass
-                                of their own (4 passes over the points instead of 6 at
-                                max_partitions = 8) — measured slower on C2 (the interval-slot
-                                counting sort costs more than the pass it saves), kept for A/B.
-                                Same splits either way */,
     PD_OPT_VERIFY_FUSED = 28  /* link stage cell verify: 0 (default) a screen pass flags the cells
                                 whose forward rows hold another root, then the flagged cells are
                                 listed and verified; 1: one pass over every cell with the screen
                                 inline (no flags, list, scan or host read) — measured slower on
                                 C2 (link 5.52 vs 5.32 ms: the flagged lanes' work diverges inside
-                                every wave), kept for A/B.  Same labels */,
-    PD_OPT_HALO_TREE = 29     /* grid train halo (two-pass form, split tree replayed, P <= 64):
-                                0 (default) every point tests every expanded box; 1: a point
-                                farther than 2 eps from every split plane on its KD path is in
-                                its owner's expanded box only — one record, no box tests — and
-                                the points near a plane are listed per tile for the full test;
-                                measured slower (C2 halo 1.36 vs 1.19 ms, C4 11.3 vs 9.4 ms: the
-                                dependent tree walk and the list cost more than the box tests),
-                                kept for A/B.  Same records either way */,
-    PD_OPT_KD_REPLAY = 30     /* pd_kd_build with final_split = 2 (DBSCAN.train's KD): 0 (default)
-                                labels in HBM, read and rewritten by each level's passes; 1 each
-                                pass recomputes the points' labels by replaying the splits
-                                decided so far (tables in LDS) — no int32 label traffic, but the
-                                walk costs more than it saves (KD C2 2.76 vs 2.55 ms, C4 18.7 vs
-                                17.1 ms), kept for A/B.  Same splits either way */
+                                every wave), kept for A/B.  Same labels */
     /* Retired in round 5 (measured A/Bs whose losing kernels were removed;
        pd_ctx_set_option returns PD_EINVAL for them, and the numbers are not
        reused): 4 LINK_MODE, 5 JUMP_ROUNDS, 9 SWEEP_VARIANT, 10 BORDER_ROOTS,
        16 SORT_PAYLOAD, 20 BORDER_LISTS, 21 LINK_JUMPS, 22 DENSE_PREFETCH,
-       23 DENSE_WAVES.  DESIGN.md §6 keeps their measurements. */
+       23 DENSE_WAVES.
+       Retired after round 6 (that round's A/Bs that lost, likewise): 27
+       KD_FUSE, 29 HALO_TREE, 30 KD_REPLAY.  DESIGN.md §6 keeps the
+       measurements of both rounds. */
 };
 
 /* pd_ctx_timings() slots (ms from HIP events on the call's stream; counters) */
@@ -470,10 +451,7 @@ int32_t pd_dense_finish(pd_ctx* ctx, const int32_t* best, int32_t* labels, uint8
  * unapplied (labels then hold the previous level's; pd_train_tree replays
  * the tree itself, pd_kd_split applies it when the labels are wanted);
  * final_split = 2: the caller needs no labels (it replays the tree itself:
- * pd_train_tree, pd_kd_labels) — the passes then replay the splits decided
- * so far from tables in LDS instead of reading and writing an int32 label
- * per point (PD_OPT_KD_REPLAY; trees of <= 256 splits), and the labels array
- * is left unspecified. */
+ * pd_train_tree, pd_kd_labels), and the labels array is left unspecified. */
 int32_t pd_kd_build(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int32_t d,
                     int32_t* labels, int32_t n_levels, const int32_t* level_sizes_host,
                     const int32_t* cur_host, const int32_t* newlab_host, int32_t final_split,

@@ -311,73 +311,21 @@ __device__ __forceinline__ int part_of_wave(const uint32_t* __restrict__ ps, int
 }
 
 // ------------------------------------------------------------------ kernels
-// The KD partition's split tree (pd_train_tree): a point's owner label is
-// found by replaying the BFS splits on its coordinates — level l, the label's
-// slot: v[axis] >= boundary moves it to the new label (the kd_pass split,
-// R:dbscan/partition.py:66-68) — so pd_train needs no owner array and the
-// partitioner no final split pass.
-struct KdTree {
-    int nl = 0;                  // levels (0: no tree)
-    int ntab[16], toff[16], eoff[16];
-    int nslot = 0, ne = 0;       // table sizes
-    const int32_t* slot;         // per level: label -> slot (-1: not split)
-    const int32_t* ax_new;       // per split: axis, new label
-    const double* bound;         // per split: boundary
+// The KD partition's split tree (pd_train_tree, kdtree.hpp): a point's owner
+// label is found by replaying the BFS splits on its coordinates, so pd_train
+// needs no owner array and the partitioner no final split pass.
+// the walk's bounds sites (PD_CHECK_BOUNDS builds)
+struct TreeCheck {
+    __device__ __forceinline__ bool operator()(bool c, int site, uint64_t idx) const {
+        return PD_OK(c, site, idx);
+    }
 };
-// tables up to this size are staged in LDS by halo_write_kernel (P <= 64)
-constexpr int kTreeSlots = 256, kTreeSplits = 128;
 
 template <typename T, int D>
 __device__ __forceinline__ int tree_owner(const KdTree& t, const int32_t* slot,
                                           const int32_t* ax_new, const double* bound,
                                           const T (&v)[D]) {
-    int lab = 0;
-    for (int l = 0; l < t.nl; ++l) {
-        if (lab >= t.ntab[l]) continue;
-        if (!PD_OK(t.toff[l] + lab < t.nslot, 1, t.toff[l] + lab)) continue;
-        const int sl = slot[t.toff[l] + lab];
-        if (sl < 0) continue;
-        const int e = t.eoff[l] + sl;
-        if (!PD_OK(e < t.ne, 2, e)) continue;
-        const int ax = ax_new[2 * e];
-        if (!PD_OK(ax >= 0 && ax < D, 3, ax)) continue;
-        T x = v[0];
-#pragma unroll
-        for (int j = 1; j < D; ++j) x = ax == j ? v[j] : x;
-        if ((double)x >= bound[e]) lab = ax_new[2 * e + 1];
-    }
-    return lab;
-}
-
-// tree_owner, and whether the point lies within `marg` (2 eps, grown) of a
-// split plane on its path, or of a non-finite one.  A point farther than
-// 2 eps from every plane on its path lies in its owner's expanded box only:
-// any other KD box is separated from it by one of those planes (the first
-// split where the two paths part), so its 2 eps expansion cannot reach it.
-template <typename T, int D>
-__device__ __forceinline__ int tree_owner_near(const KdTree& t, const int32_t* slot,
-                                               const int32_t* ax_new, const double* bound,
-                                               double marg, const T (&v)[D], bool& near) {
-    int lab = 0;
-    near = false;
-    for (int l = 0; l < t.nl; ++l) {
-        if (lab >= t.ntab[l]) continue;
-        if (!PD_OK(t.toff[l] + lab < t.nslot, 1, t.toff[l] + lab)) continue;
-        const int sl = slot[t.toff[l] + lab];
-        if (sl < 0) continue;
-        const int e = t.eoff[l] + sl;
-        if (!PD_OK(e < t.ne, 2, e)) continue;
-        const int ax = ax_new[2 * e];
-        if (!PD_OK(ax >= 0 && ax < D, 3, ax)) continue;
-        T x = v[0];
-#pragma unroll
-        for (int j = 1; j < D; ++j) x = ax == j ? v[j] : x;
-        const double xd = (double)x, b = bound[e];
-        // (2^-20 |b|: far beyond the fp64 expand's and the fp32 bounds' rounding)
-        near |= !(fabs(xd - b) > marg + 9.5367431640625e-07 * fabs(b));
-        if (xd >= b) lab = ax_new[2 * e + 1];
-    }
-    return lab;
+    return kd_tree_label<T, D>(t, slot, ax_new, bound, v, TreeCheck{});
 }
 
 // Halo records (R:dbscan/dbscan.py:136-151) in two ordered passes over the
@@ -392,15 +340,6 @@ __device__ __forceinline__ int tree_owner_near(const KdTree& t, const int32_t* s
 // The membership of each point is a bit mask over the neighbourhoods (P <=
 // 64; MASK = false recomputes instead), built branch-free in the input
 // precision with one wave-uniform grid load per neighbourhood.
-// The near-plane points of a tile, listed in LDS: (thread << 2 | step), and
-// each one's full-test record count and neighbourhood mask.
-struct NearLds {
-    uint32_t n;
-    uint32_t list[4 * kBlock];
-    uint32_t cnt[4 * kBlock];
-    unsigned long long mask[4 * kBlock];
-};
-
 template <typename T, int D, bool MASK>
 __device__ __forceinline__ void halo_points(const T* __restrict__ X, uint64_t n,
                                             const PartGrid* __restrict__ parts, int P,
@@ -427,69 +366,6 @@ __device__ __forceinline__ void halo_points(const T* __restrict__ X, uint64_t n,
     }
 }
 
-// halo_points with the split tree in LDS (P <= 64, pd_train_tree): each
-// point's owner by the tree replay; a point far from every split plane on its
-// path is in its owner's expanded box alone (tree_owner_near) — one record, no
-// box tests; the few near a plane (the halo duplicates and their
-// neighbours, ~1-2 % at the BASELINE configs) are listed block-wide and take
-// the full test, one list entry per lane.  Same counts and masks as
-// halo_points.  own[q]: the owner (-1 past n).  The caller zeroes nl.n and
-// synchronises before the call.
-template <typename T, int D>
-__device__ __forceinline__ void halo_points_tree(const T* __restrict__ X, uint64_t n,
-                                                 const PartGrid* __restrict__ parts, int P,
-                                                 uint64_t tile, const KdTree& tree,
-                                                 const int32_t* t_slot, const int32_t* t_axn,
-                                                 const double* t_bd, double marg, NearLds& nl,
-                                                 uint64_t (&idx)[4], T (&v)[4][D],
-                                                 unsigned long long (&m)[4], uint32_t (&cnt)[4],
-                                                 int (&own)[4]) {
-    const uint64_t base = tile * (4 * kBlock) + (threadIdx.x >> 6) * 256 + (threadIdx.x & 63);
-    int slotq[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        idx[q] = base + 64 * q;
-        const bool ok = idx[q] < n;
-#pragma unroll
-        for (int j = 0; j < D; ++j) v[q][j] = ok ? X[idx[q] * D + j] : T(NAN);
-        bool near = false;
-        own[q] = ok ? tree_owner_near<T, D>(tree, t_slot, t_axn, t_bd, marg, v[q], near) : -1;
-        cnt[q] = ok ? 1u : 0u;
-        m[q] = ok ? 1ull << (own[q] & 63) : 0ull;
-        slotq[q] = -1;
-        if (ok && near) {
-            slotq[q] = (int)atomicAdd(&nl.n, 1u);
-            nl.list[slotq[q]] = (threadIdx.x << 2) | (uint32_t)q;
-        }
-    }
-    __syncthreads();
-    const uint32_t nn = nl.n;
-    const uint64_t tb = tile * (4 * kBlock);
-    for (uint32_t k = threadIdx.x; k < nn; k += kBlock) {
-        const uint32_t e = nl.list[k], th = e >> 2, q = e & 3;
-        const uint64_t i = tb + (th >> 6) * 256 + (th & 63) + 64 * q;
-        T u[D];
-#pragma unroll
-        for (int j = 0; j < D; ++j) u[j] = X[i * D + j];
-        uint32_t c = 0;
-        unsigned long long mm = 0;
-        for (int Lb = 0; Lb < P; ++Lb) {
-            const bool in = in_box_t<T, D>(u, parts[Lb]);
-            c += in ? 1u : 0u;
-            mm |= (unsigned long long)in << Lb;
-        }
-        nl.cnt[k] = c;
-        nl.mask[k] = mm;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (slotq[q] >= 0) {
-            cnt[q] = nl.cnt[slotq[q]];
-            m[q] = nl.mask[slotq[q]];
-        }
-}
-
 __device__ __forceinline__ uint32_t block_sum_u32(uint32_t v) {
     __shared__ uint32_t ws[kBlock / 64];
 #pragma unroll
@@ -511,13 +387,10 @@ __device__ __forceinline__ void tile_count_out(uint32_t* tile_cnt, uint32_t c) {
 
 constexpr int kCtrs = 16;   // train counters: [0..7] lists, [8..9] big / mid cells, [10] pairs
 
-// TREE (the split tree in LDS, P <= 64): the near-plane fast path
-// (halo_points_tree); marg = 2 eps, slightly grown.
-template <typename T, int D, bool TREE>
+template <typename T, int D>
 __global__ __launch_bounds__(kBlock) void halo_tile_kernel(const T* __restrict__ X, uint64_t n,
                                                            const PartGrid* __restrict__ parts,
-                                                           int P, KdTree tree, double marg,
-                                                           uint32_t* __restrict__ tile_cnt,
+                                                           int P, uint32_t* __restrict__ tile_cnt,
                                                            uint32_t* __restrict__ ctrs,
                                                            uint32_t* __restrict__ sort_hist) {
     // the train's small counters (dup / root / core / border lists, big and
@@ -532,21 +405,7 @@ __global__ __launch_bounds__(kBlock) void halo_tile_kernel(const T* __restrict__
     T v[4][D];
     unsigned long long m[4];
     uint32_t cnt[4];
-    if constexpr (TREE) {
-        __shared__ int32_t t_slot[kTreeSlots], t_axn[2 * kTreeSplits];
-        __shared__ double t_bd[kTreeSplits];
-        __shared__ NearLds nl;
-        for (int k = threadIdx.x; k < tree.nslot; k += kBlock) t_slot[k] = tree.slot[k];
-        for (int k = threadIdx.x; k < 2 * tree.ne; k += kBlock) t_axn[k] = tree.ax_new[k];
-        for (int k = threadIdx.x; k < tree.ne; k += kBlock) t_bd[k] = tree.bound[k];
-        if (threadIdx.x == 0) nl.n = 0;
-        __syncthreads();
-        int own[4];
-        halo_points_tree<T, D>(X, n, parts, P, blockIdx.x, tree, t_slot, t_axn, t_bd, marg, nl, idx,
-                               v, m, cnt, own);
-    } else {
-        halo_points<T, D, false>(X, n, parts, P, blockIdx.x, idx, v, m, cnt);
-    }
+    halo_points<T, D, false>(X, n, parts, P, blockIdx.x, idx, v, m, cnt);
     const uint32_t t = block_sum_u32(cnt[0] + cnt[1] + cnt[2] + cnt[3]);
     if (threadIdx.x == 0) tile_count_out(tile_cnt, t);
 }
@@ -596,6 +455,8 @@ __device__ __forceinline__ K key_of(const T (&tv)[D], const KeyGrid<D>& g) {
 // Every record store is bounded by `cap` (the buffers' length): the
 // single-pass form writes before it knows the total, and a tile past the
 // capacity must not store (the host then reruns the two-pass form).
+// split-tree tables up to this size are staged in LDS (halo_stage, P <= 64)
+constexpr int kTreeSlots = 256, kTreeSplits = 128;
 template <int D>
 struct HaloLds {
     uint32_t ws[kBlock / 64];
@@ -651,8 +512,7 @@ __device__ __forceinline__ bool halo_stage(HaloLds<D>& L, const PartGrid* __rest
 
 // write the records of one tile's points from record offset wbase (this
 // wave's first record); stores at or past cap are dropped
-// PRE: the owners are already known (own_in, halo_points_tree)
-template <typename T, int D, typename K, bool MASK, bool PRE = false>
+template <typename T, int D, typename K, bool MASK>
 __device__ __forceinline__ void halo_emit(const HaloLds<D>& L, const PartGrid* __restrict__ parts,
                                           int P, const int32_t* __restrict__ owner,
                                           const KdTree& tree, bool tree_lds, uint64_t n,
@@ -660,14 +520,13 @@ __device__ __forceinline__ void halo_emit(const HaloLds<D>& L, const PartGrid* _
                                           const unsigned long long (&m)[4],
                                           const uint32_t (&cnt)[4], const uint32_t (&ex)[4],
                                           uint64_t wbase, uint64_t cap, K* __restrict__ keys,
-                                          uint32_t* __restrict__ vals, const int (&own_in)[4]) {
+                                          uint32_t* __restrict__ vals) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         if (!cnt[q]) continue;
         if (!PD_OK(idx[q] < n, 4, idx[q])) continue;
         // P == 1: neighbourhood 0
-        const int own = PRE      ? own_in[q]
-                        : owner  ? owner[idx[q]]
+        const int own = owner    ? owner[idx[q]]
                         : !tree.nl ? 0
                         : tree_lds ? tree_owner<T, D>(tree, L.t_slot, L.t_axn, L.t_bd, v[q])
                                    : tree_owner<T, D>(tree, tree.slot, tree.ax_new, tree.bound, v[q]);
@@ -703,40 +562,27 @@ __device__ __forceinline__ void halo_emit(const HaloLds<D>& L, const PartGrid* _
     }
 }
 
-template <typename T, int D, typename K, bool MASK, bool TREE = false>
+template <typename T, int D, typename K, bool MASK>
 __global__ __launch_bounds__(kBlock) void halo_write_kernel(
     const T* __restrict__ X, uint64_t n, const PartGrid* __restrict__ parts, int P,
-    const int32_t* __restrict__ owner, KdTree tree, double marg,
-    const uint64_t* __restrict__ tile_off, uint64_t cap, K* __restrict__ keys,
-    uint32_t* __restrict__ vals) {
-    static_assert(!TREE || MASK, "the near-plane path builds masks");
+    const int32_t* __restrict__ owner, KdTree tree, const uint64_t* __restrict__ tile_off,
+    uint64_t cap, K* __restrict__ keys, uint32_t* __restrict__ vals) {
     uint64_t idx[4];
     T v[4][D];
     unsigned long long m[4];
     uint32_t cnt[4], ex[4];
-    int own[4] = {0, 0, 0, 0};
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     __shared__ HaloLds<D> L;
-    __shared__ std::conditional_t<TREE, NearLds, char> nl;
-    bool tree_lds;
-    if constexpr (TREE) {
-        tree_lds = halo_stage<T, D, MASK>(L, parts, P, tree);   // (true by the host's choice)
-        if (threadIdx.x == 0) nl.n = 0;
-        __syncthreads();
-        halo_points_tree<T, D>(X, n, parts, P, blockIdx.x, tree, L.t_slot, L.t_axn, L.t_bd, marg,
-                               nl, idx, v, m, cnt, own);
-    } else {
-        halo_points<T, D, MASK>(X, n, parts, P, blockIdx.x, idx, v, m, cnt);
-        tree_lds = halo_stage<T, D, MASK>(L, parts, P, tree);
-    }
+    halo_points<T, D, MASK>(X, n, parts, P, blockIdx.x, idx, v, m, cnt);
+    const bool tree_lds = halo_stage<T, D, MASK>(L, parts, P, tree);
     const uint32_t wtot = wave_offsets<4>(cnt, ex);
     if (lane == 0) L.ws[w] = wtot;
     __syncthreads();
     uint64_t wbase = tile_off[blockIdx.x];
 #pragma unroll
     for (int u = 0; u < kBlock / 64; ++u) wbase += u < w ? L.ws[u] : 0u;
-    halo_emit<T, D, K, MASK, TREE>(L, parts, P, owner, tree, tree_lds, n, idx, v, m, cnt, ex, wbase,
-                                   cap, keys, vals, own);
+    halo_emit<T, D, K, MASK>(L, parts, P, owner, tree, tree_lds, n, idx, v, m, cnt, ex, wbase, cap,
+                             keys, vals);
 }
 
 // Single-pass halo (PD_OPT_HALO_PASSES = 1): each tile counts its records,
@@ -819,9 +665,8 @@ __global__ __launch_bounds__(kBlock) void halo1_kernel(
     uint64_t wbase = s_base;
 #pragma unroll
     for (int u = 0; u < kBlock / 64; ++u) wbase += u < w ? L.ws[u] : 0u;
-    const int own0[4] = {0, 0, 0, 0};
     halo_emit<T, D, K, MASK>(L, parts, P, owner, tree, tree_lds, n, idx, v, m, cnt, ex, wbase, cap,
-                             keys, vals, own0);
+                             keys, vals);
 }
 
 // Coordinates into key order (padded rows); also lists the records of halo
@@ -2968,63 +2813,21 @@ void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t
     PartGrid* parts = ctx.arena.get<PartGrid>("parts", P);
     const T* X = (const T*)a.X;
 
-    // the split tree (pd_train_tree): per level a label -> slot table, per
-    // split (axis, new label) and the boundary — host tables first, then ONE
-    // pinned block carries the grids and the tree (no sync between uploads)
+    // the split tree (pd_train_tree): ONE pinned block carries the grids and
+    // the tree's tables (no sync between uploads)
     KdTree tree;
-    std::vector<int32_t> t_int;
-    std::vector<double> t_bd;
-    if (!a.owner && a.tree_levels > 0) {
-        const int nl = a.tree_levels;
-        if (nl > 16) throw Error(-5, "KD split tree deeper than 16 levels");
-        std::vector<int> ntab(nl, 1), toff(nl, 0), eoff(nl, 0);
-        int nslot = 0, ne = 0;
-        for (int l = 0; l < nl; ++l) {
-            for (int k = 0; k < a.tree_sizes[l]; ++k)
-                ntab[l] = std::max(ntab[l], a.tree_cur[ne + k] + 1);
-            toff[l] = nslot;
-            eoff[l] = ne;
-            nslot += ntab[l];
-            ne += a.tree_sizes[l];
-        }
-        t_int.assign((size_t)nslot + 2 * ne, -1);
-        t_bd.assign(ne, 0.0);
-        for (int l = 0; l < nl; ++l)
-            for (int k = 0; k < a.tree_sizes[l]; ++k) {
-                const int e = eoff[l] + k, L = a.tree_cur[e];
-                if (L < 0 || L >= P || a.tree_new[e] < 0 || a.tree_new[e] >= P ||
-                    a.tree_axis[e] < 0 || a.tree_axis[e] >= D || t_int[toff[l] + L] != -1)
-                    throw Error(-1, "bad KD split tree");
-                t_int[toff[l] + L] = k;
-                t_int[nslot + 2 * e] = a.tree_axis[e];
-                t_int[nslot + 2 * e + 1] = a.tree_new[e];
-                t_bd[e] = a.tree_bound[e];
-            }
-        tree.nl = nl;
-        for (int l = 0; l < nl; ++l) {
-            tree.ntab[l] = ntab[l];
-            tree.toff[l] = toff[l];
-            tree.eoff[l] = eoff[l];
-        }
-        tree.nslot = nslot;
-        tree.ne = ne;
-    }
+    if (!a.owner && a.tree_levels > 0) tree = kd_tree_shape(a.tree_levels, a.tree_sizes, a.tree_cur);
     {
         const size_t pb = (sizeof(PartGrid) * P + 15) & ~size_t(15);
-        const size_t ib = (sizeof(int32_t) * t_int.size() + 7) & ~size_t(7);
-        const size_t tb = ib + sizeof(double) * t_bd.size();
+        const size_t tb = tree.nl ? kd_tree_bytes(tree) : 0;
         char* h = (char*)pinned(ctx, pb + tb);
+        char* dt = tree.nl ? ctx.arena.get<char>("kd_tree", tb) : nullptr;
+        if (tree.nl)   // (validates the caller's tree: before any upload)
+            kd_tree_fill(tree, a.tree_sizes, a.tree_cur, a.tree_axis, a.tree_bound, a.tree_new, D, P,
+                         h + pb, dt);
         std::memcpy(h, hparts.data(), sizeof(PartGrid) * P);
         PD_HIP(hipMemcpyAsync(parts, h, sizeof(PartGrid) * P, hipMemcpyHostToDevice, s));
-        if (tree.nl) {
-            std::memcpy(h + pb, t_int.data(), sizeof(int32_t) * t_int.size());
-            std::memcpy(h + pb + ib, t_bd.data(), sizeof(double) * t_bd.size());
-            char* dt = ctx.arena.get<char>("kd_tree", tb);
-            PD_HIP(hipMemcpyAsync(dt, h + pb, tb, hipMemcpyHostToDevice, s));
-            tree.slot = (const int32_t*)dt;
-            tree.ax_new = (const int32_t*)dt + tree.nslot;
-            tree.bound = (const double*)(dt + ib);
-        }
+        if (tree.nl) PD_HIP(hipMemcpyAsync(dt, h + pb, tb, hipMemcpyHostToDevice, s));
         // (the block is next written by a D2H copy ordered after these on s,
         // and read by the host only after a sync)
     }
@@ -3084,29 +2887,18 @@ void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t
         // two passes: tile counts, scan, write
         uint32_t* tcnt = ctx.arena.get<uint32_t>("tile_cnt", (size_t)htiles + 1);
         uint64_t* toff = ctx.arena.get<uint64_t>("tile_off", (size_t)htiles + 1);
-        // the near-plane fast path needs the split tree in LDS (P <= 64)
-        const bool tree_fast = ctx.halo_tree && P <= 64 && !a.owner && tree.nl &&
-                               tree.nslot <= kTreeSlots && tree.ne <= kTreeSplits;
-        const double marg = 2.0 * a.eps * (1.0 + 9.5367431640625e-07);
-        if (tree_fast)
-            hipLaunchKernelGGL((halo_tile_kernel<T, D, true>), dim3(htiles), dim3(kBlock), 0, s, X, n,
-                               parts, P, tree, marg, tcnt, ctrs, sort_hist);
-        else
-            hipLaunchKernelGGL((halo_tile_kernel<T, D, false>), dim3(htiles), dim3(kBlock), 0, s, X,
-                               n, parts, P, tree, marg, tcnt, ctrs, sort_hist);
+        hipLaunchKernelGGL((halo_tile_kernel<T, D>), dim3(htiles), dim3(kBlock), 0, s, X, n, parts, P,
+                           tcnt, ctrs, sort_hist);
         R64 = tile_offsets(ctx, tcnt, htiles, toff, s, true);
         if (R64 >= 0xFFFFFFFEull) throw Error(-5, "more than 2^32-2 halo records on one device");
         keys = ctx.arena.get<K>("keys", R64);
         vals = ctx.arena.get<uint32_t>("vals", R64);
-        if (tree_fast)
-            hipLaunchKernelGGL((halo_write_kernel<T, D, K, true, true>), dim3(htiles), dim3(kBlock), 0,
-                               s, X, n, parts, P, a.owner, tree, marg, toff, R64, keys, vals);
-        else if (P <= 64)
+        if (P <= 64)
             hipLaunchKernelGGL((halo_write_kernel<T, D, K, true>), dim3(htiles), dim3(kBlock), 0, s,
-                               X, n, parts, P, a.owner, tree, marg, toff, R64, keys, vals);
+                               X, n, parts, P, a.owner, tree, toff, R64, keys, vals);
         else
             hipLaunchKernelGGL((halo_write_kernel<T, D, K, false>), dim3(htiles), dim3(kBlock), 0,
-                               s, X, n, parts, P, a.owner, tree, marg, toff, R64, keys, vals);
+                               s, X, n, parts, P, a.owner, tree, toff, R64, keys, vals);
         PD_HIP(hipGetLastError());
         check_bounds(s, "halo_write_kernel");
     }

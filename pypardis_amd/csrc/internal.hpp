@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "kdtree.hpp"
 
 #include <map>
 #include <vector>
@@ -122,12 +123,10 @@ struct DenseState {
 // all-reduce of the counts) in between, stream-ordered, with no host sync.
 struct KdxState {
     bool valid = false;
-    int n_levels = 0, d = 0;
-    std::vector<int> sizes, first, ntab;
+    int d = 0;
+    KdLevels lv;                 // the schedule's table layout (kdtree.hpp)
     std::vector<int32_t> cur;
-    std::vector<size_t> off, off_d;
-    int total = 0;
-    char* tables = nullptr;      // device: per level slot_of | axis | newlab | bounds | boundary
+    char* tables = nullptr;      // device: the level tables
     double* trace = nullptr;     // device: 13 doubles per split
     double* bbox = nullptr;      // device: combined bbox (2d) + non-finite count
     double* mom = nullptr;       // device: combined moments of the current level
@@ -171,12 +170,7 @@ struct Ctx {
     unsigned long long h1_tick0 = 0;
     uint32_t h1_epoch = 0;
     double h1_ratio = 1.0;       // records per point of the last grid train (sizes the next cap)
-    bool kd_fuse = false;        // PD_OPT_KD_FUSE: kd_build fuses counts + the children's moments
-                                 // (measured slower on C2: outside the train 2.79-3.32 vs 2.61-2.96 ms)
     bool verify_fused = false;   // PD_OPT_VERIFY_FUSED: cell verify over every cell, screen inline
-    bool halo_tree = false;      // PD_OPT_HALO_TREE: halo membership tests only near split planes
-                                 // (measured slower: C2 halo 1.36 vs 1.19 ms, C4 11.3 vs 9.4 ms)
-    bool kd_replay = false;      // PD_OPT_KD_REPLAY: KD passes replay the splits instead of labels
     bool screen = true;          // fp32 screening of fp32 inputs (exact either way)
     bool sweep_stats = false;    // tally sweep candidates / union-find outcomes
     int64_t dir_budget = 32ll << 30;   // eps-grid directory bytes before cells grow

@@ -267,59 +267,9 @@ struct SplitTab {
 // take the one-point-per-lane kernels).
 constexpr int kTabLds = 256;
 // kd_pass_kernel: up to this many labels are summed per lane without the
-// LDS regroup
+// LDS regroup; more labels: one block-wide counting sort per tile, each wave
+// summing one label
 constexpr int kDirectMax = 1;
-// more labels: regroup each wave's points by label in its own LDS region
-// (false: one block-wide counting sort per tile, each wave summing one label)
-constexpr bool kWaveRegroup = false;   // measured slower on C2: 0.69 / 1.00 vs 0.61 / 0.82 ms
-
-// Label replay (kd_build, round 6): instead of reading and
-// writing an int32 label per point per pass, a pass recomputes each point's
-// label by replaying the BFS splits decided so far on its coordinates (level
-// l, the label's slot: v[axis] >= boundary moves it to the new label,
-// R:dbscan/partition.py:66-68) — the halo pass's tree_owner, from tables in
-// LDS.  Levels 0 .. nl-1; per level the label -> slot table and per split
-// (axis, new label, boundary), the axes and boundaries as the device decided
-// them (kdb_axes_kernel / kdb_boundary_kernel).
-constexpr int kMaxLevels = 16, kRSlots = 512, kRSplits = 256;
-struct ReplayTab {
-    int nl = 0;
-    int ntab[kMaxLevels], nsplit[kMaxLevels], toff[kMaxLevels], eoff[kMaxLevels];
-    const int32_t* slot[kMaxLevels];
-    const int32_t* axis[kMaxLevels];
-    const int32_t* newlab[kMaxLevels];
-    const double* boundary[kMaxLevels];
-};
-struct ReplayLds {
-    int32_t slot[kRSlots];
-    int32_t axis[kRSplits], newlab[kRSplits];
-    double bd[kRSplits];
-};
-
-__device__ __forceinline__ void replay_stage(ReplayLds& R, const ReplayTab& rp, int tid, int nt) {
-    for (int l = 0; l < rp.nl; ++l) {
-        for (int k = tid; k < rp.ntab[l]; k += nt) R.slot[rp.toff[l] + k] = rp.slot[l][k];
-        for (int k = tid; k < rp.nsplit[l]; k += nt) {
-            R.axis[rp.eoff[l] + k] = rp.axis[l][k];
-            R.newlab[rp.eoff[l] + k] = rp.newlab[l][k];
-            R.bd[rp.eoff[l] + k] = rp.boundary[l][k];
-        }
-    }
-}
-
-template <typename T, int D>
-__device__ __forceinline__ int replay_label(const ReplayLds& R, const ReplayTab& rp,
-                                            const T (&v)[D]) {
-    int lab = 0;
-    for (int l = 0; l < rp.nl; ++l) {
-        if (lab >= rp.ntab[l]) continue;
-        const int sl = R.slot[rp.toff[l] + lab];
-        if (sl < 0) continue;
-        const int e = rp.eoff[l] + sl;
-        if ((double)pick_axis<T, D>(v, R.axis[e]) >= R.bd[e]) lab = R.newlab[e];
-    }
-    return lab;
-}
 
 // NG = labels whose moments this pass accumulates (0: none); LAB: labels are
 // read (false: every point has label 0, the first level); SP: the previous
@@ -333,13 +283,10 @@ __device__ __forceinline__ int replay_label(const ReplayLds& R, const ReplayTab&
 // work per point is then that of one label, whatever NG is.
 // Block partials: NG x [count, (sum hi, lo) x D, (sumsq hi, lo) x D], then
 // the bbox [lo x D, hi x D, bad].
-// RP: labels replayed from the split tree (rp), none read or written (LAB
-// and SP unused).
-template <typename T, int D, bool LAB, bool SP, int NG, bool BB, bool RP = false>
+template <typename T, int D, bool LAB, bool SP, int NG, bool BB>
 __global__ __launch_bounds__(kBlock) void kd_pass_kernel(const T* __restrict__ X, uint64_t n,
                                                          int32_t* __restrict__ labels, SplitTab sp,
-                                                         int4 sel, double* __restrict__ part,
-                                                         ReplayTab rp) {
+                                                         int4 sel, double* __restrict__ part) {
     constexpr int K = (sizeof(T) * D <= 16) ? 2 : 1;
     constexpr int TP = 4 * K * kBlock;   // points per tile
     constexpr int NW = kBlock / 64;
@@ -350,11 +297,7 @@ __global__ __launch_bounds__(kBlock) void kd_pass_kernel(const T* __restrict__ X
     __shared__ int s_slot[SP ? kTabLds : 1], s_ax[SP ? kTabLds : 1], s_nl[SP ? kTabLds : 1];
     __shared__ double s_bd[SP ? kTabLds : 1];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    __shared__ std::conditional_t<RP, ReplayLds, char> s_rp;
-    if constexpr (RP) {
-        replay_stage(s_rp, rp, tid, kBlock);
-        __syncthreads();
-    } else if constexpr (SP) {
+    if constexpr (SP) {
         for (int k = tid; k < sp.ntab; k += kBlock) s_slot[k] = sp.slot_of[k];
         for (int k = tid; k < sp.nsplit; k += kBlock) {
             s_ax[k] = sp.axis[k];
@@ -370,8 +313,7 @@ __global__ __launch_bounds__(kBlock) void kd_pass_kernel(const T* __restrict__ X
 #pragma unroll
     for (int j = 0; j < D; ++j) s[j] = q2[j] = DD{0.0, 0.0};
     constexpr bool kDirect = NG >= 1 && NG <= kDirectMax;
-    constexpr bool kWave = NG > kDirectMax && kWaveRegroup;   // wave-local regroup
-    constexpr int ND = (kDirect || kWave) ? NG : 1;
+    constexpr int ND = kDirect ? NG : 1;
     double dc[ND];
     DD ds[ND][D], dq[ND][D];
 #pragma unroll
@@ -405,13 +347,10 @@ __global__ __launch_bounds__(kBlock) void kd_pass_kernel(const T* __restrict__ X
                     for (int j = 0; j < D; ++j) v[k][q][j] = T(0);
             }
             int lab[4] = {0, 0, 0, 0};
-            if constexpr (RP) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) lab[q] = replay_label<T, D>(s_rp, rp, v[k][q]);
-            } else if constexpr (LAB) {
+            if constexpr (LAB) {
                 if (m) load_labels4<true>(labels, ch, m, lab);
             }
-            if constexpr (SP && !RP) {
+            if constexpr (SP) {
                 bool changed = false;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -471,64 +410,6 @@ __global__ __launch_bounds__(kBlock) void kd_pass_kernel(const T* __restrict__ X
                         }
                     }
                 }
-        } else if constexpr (kWave) {
-            // each wave regroups its own 4·K·64 points by slot in its LDS
-            // region (ballot counting sort, no block barrier), then sums each
-            // slot's run into that slot's accumulators: one set of
-            // double-double sums per point, no cross-wave imbalance
-            constexpr int WP = 4 * K * 64;
-            T* wv = s_val + (size_t)w * WP * D;
-            int wc[NG], run[NG];
-#pragma unroll
-            for (int g = 0; g < NG; ++g) wc[g] = 0;
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int g = 0; g < NG; ++g) wc[g] += __popcll(__ballot(slot[k][q] == g));
-            int acc0 = 0;
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                run[g] = acc0;
-                acc0 += wc[g];
-            }
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int g = 0; g < NG; ++g) {
-                        const unsigned long long b = __ballot(slot[k][q] == g);
-                        if (slot[k][q] == g) {
-                            const int pos = run[g] + __popcll(b & lt);
-#pragma unroll
-                            for (int j = 0; j < D; ++j) wv[pos * D + j] = v[k][q][j];
-                        }
-                        run[g] += __popcll(b);
-                    }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            int start = 0;
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                for (int i = lane; i < wc[g]; i += 64) {
-                    const T* p = wv + (size_t)(start + i) * D;
-                    dc[g] += 1.0;
-#pragma unroll
-                    for (int j = 0; j < D; ++j) {
-                        const T x = p[j];
-                        const T xx = x * x;   // squared in the input precision (numpy)
-                        dd_acc(ds[g][j], (double)x);
-                        dd_acc(dq[g][j], (double)xx);
-                    }
-                }
-                start += wc[g];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         } else if constexpr (NG > 0) {
             // counting sort of the tile by slot: wave tallies, then positions
             int wc[NGa];
@@ -594,7 +475,7 @@ __global__ __launch_bounds__(kBlock) void kd_pass_kernel(const T* __restrict__ X
     constexpr int WM = NG * G;
     constexpr int WB = BB ? 2 * D + 1 : 0;
     constexpr int W = WM + WB;
-    if constexpr (kDirect || kWave) {
+    if constexpr (kDirect) {
         // every wave holds all NG slots: fold them into the regroup layout
         // (slot g in wave g's row) through LDS, waves in order
         __shared__ double sd[NW][NG][G];
@@ -791,10 +672,8 @@ __global__ __launch_bounds__(kBlock) void counts4_kernel(
     const T* __restrict__ X, uint64_t n, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ slot_of, int n_label_tab, const int32_t* __restrict__ axis,
     const double* __restrict__ bounds, int n_sel, int mono, int rep,
-    unsigned long long* __restrict__ out, ReplayTab rp) {
+    unsigned long long* __restrict__ out) {
     extern __shared__ unsigned int lcnt[];   // rep * n_sel * 8
-    __shared__ ReplayLds s_rp;   // (rp.nl > 0: labels replayed instead of read)
-    replay_stage(s_rp, rp, threadIdx.x, kBlock);
     __shared__ int s_slot[kTabLds], s_ax[kTabLds];
     __shared__ double s_bd[kTabLds * 7];
     for (int k = threadIdx.x; k < rep * n_sel * 8; k += kBlock) lcnt[k] = 0;
@@ -809,12 +688,7 @@ __global__ __launch_bounds__(kBlock) void counts4_kernel(
         T v[4][D];
         const int m = load_chunk<T, D, true>(X, n, ch, v);
         int lab[4];
-        if (rp.nl) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) lab[q] = replay_label<T, D>(s_rp, rp, v[q]);
-        } else {
-            load_labels4<true>(labels, ch, m, lab);
-        }
+        load_labels4<true>(labels, ch, m, lab);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (q >= m || lab[q] < 0 || lab[q] >= n_label_tab) continue;
@@ -847,14 +721,11 @@ __global__ __launch_bounds__(kBlock) void counts4_kernel(
 // serialise): c[s][i] = #points of slot s with v[axis] < bound i, c[s][7] =
 // #points of slot s; one wave reduction and one LDS atomic per counter and
 // wave at the end.  Labels < kTabLds.
-template <typename T, int D, int NS, bool RP = false>
+template <typename T, int D, int NS>
 __global__ __launch_bounds__(kBlock) void counts_reg_kernel(
     const T* __restrict__ X, uint64_t n, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ slot_of, int n_label_tab, const int32_t* __restrict__ axis,
-    const double* __restrict__ bounds, int n_sel, unsigned long long* __restrict__ out,
-    ReplayTab rp) {
-    __shared__ std::conditional_t<RP, ReplayLds, char> s_rp;
-    if constexpr (RP) replay_stage(s_rp, rp, threadIdx.x, kBlock);
+    const double* __restrict__ bounds, int n_sel, unsigned long long* __restrict__ out) {
     __shared__ int s_slot[kTabLds];
     __shared__ unsigned int s_cnt[NS * 8];
     for (int k = threadIdx.x; k < n_label_tab; k += kBlock) s_slot[k] = slot_of[k];
@@ -879,12 +750,7 @@ __global__ __launch_bounds__(kBlock) void counts_reg_kernel(
         T v[4][D];
         const int m = load_chunk<T, D, true>(X, n, ch, v);
         int lab[4] = {0, 0, 0, 0};   // labels == nullptr: every point in label 0
-        if constexpr (RP) {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) lab[p] = replay_label<T, D>(s_rp, rp, v[p]);
-        } else if (labels) {
-            load_labels4<true>(labels, ch, m, lab);
-        }
+        if (labels) load_labels4<true>(labels, ch, m, lab);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const int L = lab[p];
@@ -912,275 +778,6 @@ __global__ __launch_bounds__(kBlock) void counts_reg_kernel(
     __syncthreads();
     for (int k = threadIdx.x; k < n_sel * 8 && k < NS * 8; k += kBlock)
         if (s_cnt[k]) atomicAdd(&out[k], (unsigned long long)s_cnt[k]);
-}
-
-// ---------------------------------------------------------------- fused level pass 2
-// Counts and the NEXT level's moments in one read of X (kd_build; VERDICT
-// r05 #6): apply the previous level's split (SP, R:dbscan/partition.py:66-68;
-// labels written back where they change, or all of them when none were
-// written yet, !LAB), count this level's seven candidate compares per split
-// (:60-63, counts_reg_kernel's register counters: c[s][i] = #(v[axis] <
-// bound i), c[s][7] = #points) and, MOM, the double-double moments (:86-89)
-// of every (split, interval) pair — interval q = #{i : v[axis] >= bound i}
-// in 0..7.  The bounds mean + (i - 3) 0.3 std are non-decreasing, so the
-// child a boundary i* makes is a run of intervals: left (v < bound i*) is q
-// <= i*, right (v >= bound i*, the split's predicate) is q > i*.  The next
-// level's moments are then dd sums of whole intervals (kdb_children_kernel),
-// with no moments pass of their own; exact double-double sums do not depend
-// on grouping, so they equal that pass's totals.
-// MOM tiles: a counting sort of the tile by interval slot in LDS, then wave
-// w sums slots w, w + NW, ... (NS * 8 / NW slots per wave, in registers).
-template <typename T, int D, bool LAB, bool SP, int NS, bool MOM, int NW>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(
-    (MOM && NS == 1 && sizeof(T) * D <= 12) ? 4 : 1))) void kdf_kernel(
-    const T* __restrict__ X, uint64_t n, int32_t* __restrict__ labels, SplitTab sp,
-    const int32_t* __restrict__ slot_of, int ntab, const int32_t* __restrict__ axis,
-    const double* __restrict__ bounds, int n_sel, unsigned long long* __restrict__ cnt_out,
-    double* __restrict__ part) {
-    constexpr int NT = 64 * NW;
-    constexpr int K = (sizeof(T) * D <= 16) ? 2 : 1;
-    constexpr int TP = 4 * K * NT;   // points per tile
-    constexpr int NI = NS * 8;       // interval slots
-    constexpr int SPW = MOM ? NI / NW : 1;
-    constexpr int G = 1 + 4 * D;
-    static_assert(!MOM || (NI % NW == 0 && SPW >= 1), "slots per wave");
-    __shared__ T s_val[MOM ? TP * D : 1];
-    // per (wave, slot): running ranks, then the wave's first position; per
-    // slot: the tile's total and first position
-    __shared__ int s_lcnt[MOM ? NW : 1][MOM ? NI : 1], s_woff[MOM ? NW : 1][MOM ? NI : 1];
-    __shared__ int s_tot[MOM ? NI : 1], s_seg[MOM ? NI : 1];
-    // MOM: this level's axes and bounds by slot (one lookup per point, no
-    // per-slot branches) and the block's points per (slot, interval) — the
-    // counts follow from them: v < bound i  <=>  interval <= i
-    __shared__ int s_axc[MOM ? NS : 1];
-    __shared__ double s_bnd[MOM ? NS * 7 : 1];
-    __shared__ unsigned int s_icnt[MOM ? NI : 1];
-    __shared__ int s_slot[SP ? kTabLds : 1], s_ax[SP ? kTabLds : 1], s_nl[SP ? kTabLds : 1];
-    __shared__ double s_bd[SP ? kTabLds : 1];
-    __shared__ int s_cur[kTabLds];
-    __shared__ unsigned int s_cnt[NS * 8];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    if constexpr (SP) {
-        for (int k = tid; k < sp.ntab; k += NT) s_slot[k] = sp.slot_of[k];
-        for (int k = tid; k < sp.nsplit; k += NT) {
-            s_ax[k] = sp.axis[k];
-            s_bd[k] = sp.boundary[k];
-            s_nl[k] = sp.newlab[k];
-        }
-    }
-    for (int k = tid; k < ntab; k += NT) s_cur[k] = slot_of[k];
-    for (int k = tid; k < NS * 8; k += NT) s_cnt[k] = 0;
-    if constexpr (MOM) {
-        for (int k = tid; k < NW * NI; k += NT) (&s_lcnt[0][0])[k] = 0;
-        for (int k = tid; k < NI; k += NT) s_icnt[k] = 0;
-        for (int k = tid; k < NS; k += NT) s_axc[k] = k < n_sel ? axis[k] : 0;
-        for (int k = tid; k < NS * 7; k += NT) s_bnd[k] = k < n_sel * 7 ? bounds[k] : 0.0;
-    }
-    int ax[NS];
-    double b[NS][7];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-        ax[q] = q < n_sel ? axis[q] : 0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) b[q][i] = q < n_sel ? bounds[q * 7 + i] : 0.0;
-    }
-    __syncthreads();
-    uint32_t c[NS][8];
-#pragma unroll
-    for (int q = 0; q < NS; ++q)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) c[q][i] = 0;
-    double ac[SPW];
-    DD as[SPW][D], aq[SPW][D];
-#pragma unroll
-    for (int o = 0; o < SPW; ++o) {
-        ac[o] = 0.0;
-#pragma unroll
-        for (int j = 0; j < D; ++j) as[o][j] = aq[o][j] = DD{0.0, 0.0};
-    }
-    const uint64_t nch = (n + 3) / 4;
-    const uint64_t ntile = (n + TP - 1) / TP;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    for (uint64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
-        T v[K][4][D];
-        int slot[K][4];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const uint64_t ch = t * (TP / 4) + (uint64_t)k * NT + tid;
-            int m = 0;
-            if (ch < nch) {
-                m = load_chunk<T, D, true>(X, n, ch, v[k]);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) v[k][q][j] = T(0);
-            }
-            int lab[4] = {0, 0, 0, 0};
-            if constexpr (LAB) {
-                if (m) load_labels4<true>(labels, ch, m, lab);
-            }
-            if constexpr (SP) {
-                bool changed = false;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int L = lab[q];
-                    if (q >= m || L < 0 || L >= sp.ntab) continue;
-                    const int a = s_slot[L];
-                    if (a < 0) continue;
-                    const double x = (double)pick_axis<T, D>(v[k][q], s_ax[a]);
-                    if (x >= s_bd[a]) {
-                        lab[q] = s_nl[a];
-                        changed = true;
-                    }
-                }
-                if (m && (changed || !LAB)) store_labels4<true>(labels, ch, m, lab);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int L = lab[q];
-                const int sl = (q < m && L >= 0 && L < ntab) ? s_cur[L] : -1;
-                slot[k][q] = -1;
-                if constexpr (MOM) {
-                    if (sl >= 0) {
-                        const double x = (double)pick_axis<T, D>(v[k][q], s_axc[sl]);
-                        int qi = 0;
-#pragma unroll
-                        for (int i = 0; i < 7; ++i) qi += x >= s_bnd[sl * 7 + i] ? 1 : 0;
-                        slot[k][q] = sl * 8 + qi;
-                    }
-                } else {
-#pragma unroll
-                    for (int sI = 0; sI < NS; ++sI) {
-                        if (sl != sI) continue;
-                        const double x = (double)pick_axis<T, D>(v[k][q], ax[sI]);
-                        ++c[sI][7];
-#pragma unroll
-                        for (int i = 0; i < 7; ++i) c[sI][i] += x < b[sI][i] ? 1u : 0u;
-                    }
-                }
-            }
-        }
-        if constexpr (MOM) {
-            // counting sort of the tile by interval slot: each item's rank
-            // among its wave's items of the slot (5-ballot peer mask, running
-            // per-(wave, slot) counters in LDS, as rsort's pass_kernel ranks
-            // digits), then the slots' and waves' starts, then the staging
-            int rk[K][4];
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int sl = slot[k][q];
-                    const unsigned u5 = sl < 0 ? 31u : (unsigned)sl;
-                    unsigned long long mk = ~0ull;
-#pragma unroll
-                    for (int bt = 0; bt < 5; ++bt) {
-                        const unsigned long long bb = __ballot((u5 >> bt) & 1u);
-                        mk &= ((u5 >> bt) & 1u) ? bb : ~bb;
-                    }
-                    const int base = sl >= 0 ? s_lcnt[w][sl] : 0;
-                    rk[k][q] = base + __popcll(mk & lt);
-                    if (sl >= 0 && (mk & lt) == 0) s_lcnt[w][sl] = base + __popcll(mk);
-                }
-            __syncthreads();
-            if (tid < NI) {
-                int a = 0;
-#pragma unroll
-                for (int u = 0; u < NW; ++u) a += s_lcnt[u][tid];
-                s_tot[tid] = a;
-                s_icnt[tid] += (unsigned int)a;
-            }
-            __syncthreads();
-            if (tid < NI) {
-                int a = 0;
-                for (int h = 0; h < tid; ++h) a += s_tot[h];
-                s_seg[tid] = a;
-#pragma unroll
-                for (int u = 0; u < NW; ++u) {
-                    s_woff[u][tid] = a;
-                    a += s_lcnt[u][tid];
-                    s_lcnt[u][tid] = 0;   // (restarted for the next tile)
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int sl = slot[k][q];
-                    if (sl < 0) continue;
-                    const int pos = s_woff[w][sl] + rk[k][q];
-#pragma unroll
-                    for (int j = 0; j < D; ++j) s_val[pos * D + j] = v[k][q][j];
-                }
-            __syncthreads();
-#pragma unroll
-            for (int o = 0; o < SPW; ++o) {
-                const int g = w + o * NW;
-                const int start = s_seg[g], len = s_tot[g];
-                for (int i = lane; i < len; i += 64) {
-                    const T* p = s_val + (size_t)(start + i) * D;
-                    ac[o] += 1.0;
-#pragma unroll
-                    for (int j = 0; j < D; ++j) {
-                        const T x = p[j];
-                        const T xx = x * x;   // squared in the input precision (numpy)
-                        dd_acc(as[o][j], (double)x);
-                        dd_acc(aq[o][j], (double)xx);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if constexpr (!MOM) {
-        // counts: one wave reduction and one LDS atomic per counter and wave
-#pragma unroll
-        for (int q = 0; q < NS; ++q)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                uint32_t x = c[q][i];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o, 64);
-                if (lane == 0 && x) atomicAdd(&s_cnt[q * 8 + i], x);
-            }
-    } else {
-        // counts from the intervals: #(v < bound i) = points in intervals
-        // <= i (bounds non-decreasing; NaN bounds: v < NaN never holds)
-        __syncthreads();
-        if (tid < NS * 8) {
-            const int sI = tid >> 3, i = tid & 7;
-            unsigned int x = 0;
-            for (int q = 0; q < 8; ++q) x += (i == 7 || q <= i) ? s_icnt[sI * 8 + q] : 0u;
-            if (i < 7 && isnan(s_bnd[sI * 7 + i])) x = 0;
-            s_cnt[tid] = x;
-        }
-    }
-    if constexpr (MOM) {
-        // each slot has one owner wave: its lane 0 writes the block partial
-        double* out = part + (uint64_t)blockIdx.x * NI * G;
-#pragma unroll
-        for (int o = 0; o < SPW; ++o) {
-            const int g = w + o * NW;
-            const double x = wave_sum(ac[o]);
-            if (lane == 0) out[g * G] = x;
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const DD a = wave_dd(as[o][j]);
-                const DD q2 = wave_dd(aq[o][j]);
-                if (lane == 0) {
-                    out[g * G + 1 + 2 * j] = a.hi;
-                    out[g * G + 2 + 2 * j] = a.lo;
-                    out[g * G + 1 + 2 * D + 2 * j] = q2.hi;
-                    out[g * G + 2 + 2 * D + 2 * j] = q2.lo;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int k = tid; k < n_sel * 8 && k < NS * 8; k += NT)
-        if (s_cnt[k]) atomicAdd(&cnt_out[k], (unsigned long long)s_cnt[k]);
 }
 
 // ---------------------------------------------------------------- split
@@ -1493,7 +1090,7 @@ void run_pass(Ctx& ctx, const T* X, int64_t n, int32_t* labels, const SplitTab& 
     const int nb = (int)std::min<int64_t>(resident, std::max<int64_t>(1, (n + TP - 1) / TP));
     double* part = ctx.arena.get<double>("pass_part", (size_t)nb * (W > 0 ? W : 1));
     hipLaunchKernelGGL((kd_pass_kernel<T, D, LAB, SP, NG, BB>), dim3(nb), dim3(kBlock), 0, s,
-                       X, (uint64_t)n, labels, sp, sel, part, ReplayTab{});
+                       X, (uint64_t)n, labels, sp, sel, part);
     PD_HIP(hipGetLastError());
     res.assign(W, 0.0);
     if constexpr (W > 0) {
@@ -1627,7 +1224,7 @@ void kd_counts(Ctx& ctx, const void* X, int dtype, int64_t n, int d, const int32
                     constexpr int NS = decltype(NSc)::value;
                     hipLaunchKernelGGL((counts_reg_kernel<T, D, NS>), dim3(nb4), dim3(kBlock), 0, s,
                                        (const T*)X, (uint64_t)n, labels, t.slot_of, t.ntab, t.axis,
-                                       t.dbl, n_sel, dcnt, ReplayTab{});
+                                       t.dbl, n_sel, dcnt);
                 };
                 if (n_sel == 1)
                     go(std::integral_constant<int, 1>{});
@@ -1647,7 +1244,7 @@ void kd_counts(Ctx& ctx, const void* X, int dtype, int64_t n, int d, const int32
                 hipLaunchKernelGGL((counts4_kernel<T, D>), dim3(nb4), dim3(kBlock),
                                    sizeof(unsigned int) * rep * n_sel * 8, s, (const T*)X,
                                    (uint64_t)n, labels, t.slot_of, t.ntab, t.axis, t.dbl, n_sel,
-                                   mono ? 1 : 0, rep, dcnt, ReplayTab{});
+                                   mono ? 1 : 0, rep, dcnt);
             });
         });
     } else
@@ -1787,25 +1384,11 @@ __global__ void kdb_boundary_kernel(const unsigned long long* __restrict__ cnt, 
     t[12] = boundary[k];
 }
 
-// The next level's moments from this level's interval moments (kdf_kernel):
-// split k's left child is its intervals q <= i* (i* = the chosen candidate,
-// trace[11]), the right child q > i*; dst[2k + side] = the child's slot in the
-// next level (-1: not split there).  Counts are exact integers; the sums are
-// double-double additions of whole intervals (exact, so equal to a moments
-// pass over the child).
 // Labels from a finished split tree (pd_kd_labels): replay every level per
 // point, tables read through the caches (a one-off pass on request).
-struct TreeG {
-    int nl;
-    int ntab[kMaxLevels], toff[kMaxLevels], eoff[kMaxLevels];
-    const int32_t* slot;     // concatenated per level: label -> split index in the level (-1)
-    const int32_t* ax_new;   // per split: axis, new label
-    const double* bound;     // per split
-};
-
 template <typename T, int D>
 __global__ __launch_bounds__(kBlock) void kd_label_kernel(const T* __restrict__ X, uint64_t n,
-                                                          int32_t* __restrict__ labels, TreeG t) {
+                                                          int32_t* __restrict__ labels, KdTree t) {
     const uint64_t nch = (n + 3) / 4;
     for (uint64_t ch = (uint64_t)blockIdx.x * kBlock + threadIdx.x; ch < nch;
          ch += (uint64_t)gridDim.x * kBlock) {
@@ -1813,68 +1396,32 @@ __global__ __launch_bounds__(kBlock) void kd_label_kernel(const T* __restrict__ 
         const int m = load_chunk<T, D, true>(X, n, ch, v);
         int lab[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int L = 0;
-            for (int l = 0; l < t.nl; ++l) {
-                if (L >= t.ntab[l]) continue;
-                const int sl = t.slot[t.toff[l] + L];
-                if (sl < 0) continue;
-                const int e = t.eoff[l] + sl;
-                if ((double)pick_axis<T, D>(v[q], t.ax_new[2 * e]) >= t.bound[e]) L = t.ax_new[2 * e + 1];
-            }
-            lab[q] = L;
-        }
+        for (int q = 0; q < 4; ++q) lab[q] = kd_tree_label<T, D>(t, t.slot, t.ax_new, t.bound, v[q]);
         store_labels4<true>(labels, ch, m, lab);
-    }
-}
-
-__global__ void kdb_children_kernel(const double* __restrict__ fin, int S, int G,
-                                    const double* __restrict__ trace,
-                                    const int32_t* __restrict__ dst, double* __restrict__ mom) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int k = idx >> 1, side = idx & 1;
-    if (k >= S) return;
-    const int j = dst[2 * k + side];
-    if (j < 0) return;
-    const int bi = (int)trace[(size_t)k * kTrace + 11];
-    const int q0 = side ? bi + 1 : 0, q1 = side ? 7 : bi;
-    double* o = mom + (size_t)j * G;
-    double c = 0.0;
-    for (int q = q0; q <= q1; ++q) c += fin[((size_t)k * 8 + q) * G];
-    o[0] = c;
-    for (int r = 1; r < G; r += 2) {
-        DD a{0.0, 0.0};
-        for (int q = q0; q <= q1; ++q) {
-            const double* p = fin + ((size_t)k * 8 + q) * G;
-            a = dd_add(a, DD{p[r], p[r + 1]});
-        }
-        o[r] = a.hi;
-        o[r + 1] = a.lo;
     }
 }
 
 namespace {
 // run_pass without the host sync: the finished quantities stay on the device
 // (fin: NG x G moments, then the bbox; may be null when the pass has none).
-// RP: labels replayed from rp (kd_pass_kernel), none read or written.
-template <typename T, int D, bool LAB, bool SP, int NG, bool BB, bool RP = false>
+template <typename T, int D, bool LAB, bool SP, int NG, bool BB>
 void run_pass_dev(Ctx& ctx, const T* X, int64_t n, int32_t* labels, const SplitTab& sp, int4 sel,
-                  double* fin, hipStream_t s, const ReplayTab& rp = ReplayTab{}) {
+                  double* fin, hipStream_t s) {
     constexpr int G = 1 + 4 * D, WM = NG * G, W = WM + (BB ? 2 * D + 1 : 0);
     constexpr int TP = 4 * kBlock * ((sizeof(T) * D <= 16) ? 2 : 1);
     static int resident = 0;
     if (!resident) {
         int per_cu = 0, dev = 0, cus = 0;
         PD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, reinterpret_cast<const void*>(&kd_pass_kernel<T, D, LAB, SP, NG, BB, RP>), kBlock, 0));
+            &per_cu, reinterpret_cast<const void*>(&kd_pass_kernel<T, D, LAB, SP, NG, BB>), kBlock, 0));
         PD_HIP(hipGetDevice(&dev));
         PD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         resident = std::max(1, per_cu) * std::max(1, cus);
     }
     const int nb = (int)std::min<int64_t>(resident, std::max<int64_t>(1, (n + TP - 1) / TP));
     double* part = ctx.arena.get<double>("pass_part", (size_t)nb * (W > 0 ? W : 1));
-    hipLaunchKernelGGL((kd_pass_kernel<T, D, LAB, SP, NG, BB, RP>), dim3(nb), dim3(kBlock), 0, s,
-                       X, (uint64_t)n, labels, sp, sel, part, rp);
+    hipLaunchKernelGGL((kd_pass_kernel<T, D, LAB, SP, NG, BB>), dim3(nb), dim3(kBlock), 0, s,
+                       X, (uint64_t)n, labels, sp, sel, part);
     PD_HIP(hipGetLastError());
     if constexpr (W > 0) {
         hipLaunchKernelGGL(kd_finish_kernel, dim3(W), dim3(kBlock), 0, s, part, nb, WM, G, D, W,
@@ -1882,54 +1429,114 @@ void run_pass_dev(Ctx& ctx, const T* X, int64_t n, int32_t* labels, const SplitT
         PD_HIP(hipGetLastError());
     }
 }
+
+// The pieces pd_kd_build and pd_kdx_* share (the two drivers differ in which
+// passes read labels and where they synchronise; the work of a level does not).
+
+inline SplitTab split_tab(const KdLevel& p) {
+    return SplitTab{p.slot, p.ntab, p.axis, p.boundary, p.newlab, p.S};
+}
+
+// A level's moments, kGroup labels per pass, into out (S x G): the first pass
+// applies the previous level's split `prev` on the way.  labels_written:
+// some earlier pass wrote the labels (false: all 0 so far, not read — the
+// first pass then writes every label).
+template <typename T, int D>
+void level_moments(Ctx& ctx, const T* X, int64_t n, int32_t* labels, bool labels_written,
+                   const KdLevel& prev, const int32_t* sel, int S, double* out, hipStream_t s) {
+    constexpr int G = 1 + 4 * D;
+    const SplitTab sp = split_tab(prev);
+    const SplitTab none{nullptr, 0, nullptr, nullptr, nullptr, 0};
+    for (int g0 = 0; g0 < S; g0 += kGroup) {
+        const int ng = std::min(S - g0, kGroup);
+        int4 sl = make_int4(-2, -2, -2, -2);
+        for (int g = 0; g < ng; ++g) (&sl.x)[g] = sel[g0 + g];
+        dispatch_ng(ng, [&](auto NGc) {
+            constexpr int NG = decltype(NGc)::value;
+            if (g0 == 0 && !labels_written)
+                run_pass_dev<T, D, false, true, NG, false>(ctx, X, n, labels, sp, sl, out, s);
+            else if (g0 == 0)
+                run_pass_dev<T, D, true, true, NG, false>(ctx, X, n, labels, sp, sl, out, s);
+            else
+                run_pass_dev<T, D, true, false, NG, false>(ctx, X, n, labels, none, sl,
+                                                           out + (size_t)g0 * G, s);
+        });
+    }
+}
+
+// A level's candidate counts into out (S x 8, zeroed by the caller): register
+// counters up to four splits, LDS histograms beyond.  labels_written as in
+// level_moments (false: the register form takes every point as label 0).
+template <typename T, int D>
+void level_counts(const T* X, int64_t n, const int32_t* labels, bool labels_written,
+                  const KdLevel& v, unsigned long long* out, hipStream_t s) {
+    const unsigned nb4 = grid_for((n + 3) / 4, 2048);
+    const int S = v.S;
+    if (S <= 4) {
+        auto go = [&](auto NSc) {
+            constexpr int NS = decltype(NSc)::value;
+            hipLaunchKernelGGL((counts_reg_kernel<T, D, NS>), dim3(nb4), dim3(kBlock), 0, s, X,
+                               (uint64_t)n, labels_written ? labels : nullptr, v.slot, v.ntab,
+                               v.axis, v.bounds, S, out);
+        };
+        if (S == 1)
+            go(std::integral_constant<int, 1>{});
+        else if (S == 2)
+            go(std::integral_constant<int, 2>{});
+        else
+            go(std::integral_constant<int, 4>{});
+    } else {
+        int rep = kRep;
+        while (rep > 1 && (size_t)rep * S * 8 * sizeof(unsigned int) > 48 * 1024) rep >>= 1;
+        hipLaunchKernelGGL((counts4_kernel<T, D>), dim3(nb4), dim3(kBlock),
+                           sizeof(unsigned int) * rep * S * 8, s, X, (uint64_t)n, labels, v.slot,
+                           v.ntab, v.axis, v.bounds, S, 0, rep, out);
+    }
+    PD_HIP(hipGetLastError());
+}
+
+// The last level's split alone (labels_written as in level_moments).
+template <typename T, int D>
+void final_split_pass(Ctx& ctx, const T* X, int64_t n, int32_t* labels, bool labels_written,
+                      const KdLevel& last, hipStream_t s) {
+    const int4 nosel = make_int4(-2, -2, -2, -2);
+    if (!labels_written)
+        run_pass_dev<T, D, false, true, 0, false>(ctx, X, n, labels, split_tab(last), nosel, nullptr, s);
+    else
+        run_pass_dev<T, D, true, true, 0, false>(ctx, X, n, labels, split_tab(last), nosel, nullptr, s);
+}
+
+// Pinned bytes of read_trace_bbox (a caller that staged tables in the pinned
+// block asks for at least this much up front, so the read-back never grows it)
+inline size_t trace_bbox_bytes(int total) {
+    return sizeof(double) * ((size_t)total * kTrace + 2 * kMaxDim + 8);
+}
+
+// One copy back: the trace and the bbox (2 d + the non-finite count).  Syncs.
+void read_trace_bbox(Ctx& ctx, const double* trace, int total, const double* bbox_dev, int d,
+                     double* trace_out, double* lohi, int64_t* bad, hipStream_t s) {
+    double* h = (double*)pinned(ctx, trace_bbox_bytes(total));
+    PD_HIP(hipMemcpyAsync(h, trace, sizeof(double) * total * kTrace, hipMemcpyDeviceToHost, s));
+    PD_HIP(hipMemcpyAsync(h + (size_t)total * kTrace, bbox_dev, sizeof(double) * (2 * d + 1),
+                          hipMemcpyDeviceToHost, s));
+    sync(s);
+    std::memcpy(trace_out, h, sizeof(double) * total * kTrace);
+    for (int j = 0; j < 2 * d; ++j) lohi[j] = h[(size_t)total * kTrace + j];
+    if (bad) *bad = (int64_t)h[(size_t)total * kTrace + 2 * d];
+}
 }  // namespace
 
-// final_mode: 0 leave the labels at the last level's labels (its split not
-// applied), 1 apply the last split too, 2 the caller needs no labels at all
-// (it replays the split tree itself: pd_train_tree, pd_kd_labels) — the
-// levels then replay the splits instead of reading and writing labels
-// (ctx.kd_replay, the tables fitting ReplayLds).
 void kd_labels(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int32_t* labels,
                int n_levels, const int32_t* sizes, const int32_t* cur, const int32_t* axis,
                const double* bound, const int32_t* newl, hipStream_t s) {
     if (n <= 0) return;
     if (!vec_ok(d, X, labels)) throw Error(-5, "kd_labels: d <= 4, 16-byte aligned inputs only");
-    if (n_levels > kMaxLevels) throw Error(-5, "kd_labels: more than 16 levels");
-    TreeG t{};
-    t.nl = n_levels;
-    std::vector<int32_t> ints;
-    std::vector<double> bd;
-    int ne = 0, nslot = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        int nt = 1;
-        for (int k = 0; k < sizes[l]; ++k) nt = std::max(nt, cur[ne + k] + 1);
-        t.ntab[l] = nt;
-        t.toff[l] = nslot;
-        t.eoff[l] = ne;
-        nslot += nt;
-        ne += sizes[l];
-    }
-    ints.assign((size_t)nslot + 2 * ne, -1);
-    bd.assign(std::max(ne, 1), 0.0);
-    for (int l = 0; l < n_levels; ++l)
-        for (int k = 0; k < sizes[l]; ++k) {
-            const int e = t.eoff[l] + k, L = cur[e];
-            if (L < 0 || L >= t.ntab[l] || axis[e] < 0 || axis[e] >= d || newl[e] < 0)
-                throw Error(-1, "kd_labels: bad split tree");
-            ints[t.toff[l] + L] = k;
-            ints[nslot + 2 * e] = axis[e];
-            ints[nslot + 2 * e + 1] = newl[e];
-            bd[e] = bound[e];
-        }
-    const size_t ib = (sizeof(int32_t) * ints.size() + 7) & ~size_t(7);
-    char* h = (char*)pinned(ctx, ib + sizeof(double) * bd.size());
-    std::memcpy(h, ints.data(), sizeof(int32_t) * ints.size());
-    std::memcpy(h + ib, bd.data(), sizeof(double) * bd.size());
-    char* dt = ctx.arena.get<char>("kdl_tables", ib + sizeof(double) * bd.size());
-    PD_HIP(hipMemcpyAsync(dt, h, ib + sizeof(double) * bd.size(), hipMemcpyHostToDevice, s));
-    t.slot = (const int32_t*)dt;
-    t.ax_new = (const int32_t*)dt + nslot;
-    t.bound = (const double*)(dt + ib);
+    KdTree t = kd_tree_shape(n_levels, sizes, cur);
+    const size_t tb = std::max(kd_tree_bytes(t), sizeof(double));   // (no levels: no tables)
+    char* h = (char*)pinned(ctx, tb);
+    char* dt = ctx.arena.get<char>("kdl_tables", tb);
+    kd_tree_fill(t, sizes, cur, axis, bound, newl, d, std::numeric_limits<int32_t>::max(), h, dt);
+    PD_HIP(hipMemcpyAsync(dt, h, tb, hipMemcpyHostToDevice, s));
     const unsigned nb = grid_for((n + 3) / 4, 4096);
     dispatch_t(dtype, [&](auto tp) {
         using T = std::remove_pointer_t<decltype(tp)>;
@@ -1943,6 +1550,10 @@ void kd_labels(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int32_t* la
     sync(s);   // (the pinned block is reused by the next upload)
 }
 
+// final_mode: 0 leave the labels at the last level's labels (its split not
+// applied), 1 apply the last split too, 2 the caller needs no labels at all
+// (it replays the split tree itself: pd_train_tree, pd_kd_labels) — as 0,
+// the labels array then holds no promise.
 void kd_build(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int32_t* labels, int n_levels,
               const int32_t* sizes, const int32_t* cur, const int32_t* newl, int final_mode,
               double* trace_out, double* lohi, int64_t* bad, hipStream_t s) {
@@ -1950,106 +1561,17 @@ void kd_build(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int32_t* lab
     if (n <= 0 || n_levels <= 0) throw Error(-1, "kd_build: no points or no levels");
     if (ctx.seq_moments || !vec_ok(d, X, labels))
         throw Error(-5, "kd_build: d <= 4, 16-byte aligned inputs and exact sums only");
-    // per level: slot_of[ntab] | axis[S] | newlab[S] | (pad 8) bounds[7 S] | boundary[S]
-    std::vector<size_t> off(n_levels + 1, 0), off_d(n_levels, 0), first(n_levels, 0);
-    std::vector<int> ntab(n_levels, 1);
-    int total = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        const int S = sizes[l];
-        if (S < 1 || S > kTabLds) throw Error(-5, "kd_build: level too wide");
-        first[l] = total;
-        for (int k = 0; k < S; ++k) {
-            const int L = cur[total + k], N = newl[total + k];
-            if (L < 0 || L >= kTabLds || N < 0) throw Error(-5, "kd_build: labels beyond the LDS tables");
-            ntab[l] = std::max(ntab[l], L + 1);
-        }
-        const size_t ints = (size_t)ntab[l] + 2 * S;
-        off_d[l] = off[l] + ((sizeof(int32_t) * ints + 7) & ~size_t(7));
-        off[l + 1] = off_d[l] + sizeof(double) * 8 * S;
-        total += S;
-    }
-    char* h = (char*)pinned(ctx, off[n_levels] + sizeof(double) * ((size_t)total * kTrace + 16));
-    std::memset(h, 0, off[n_levels]);
-    for (int l = 0; l < n_levels; ++l) {
-        int32_t* slot = (int32_t*)(h + off[l]);
-        const int S = sizes[l];
-        for (int k = 0; k < ntab[l]; ++k) slot[k] = -1;
-        for (int k = 0; k < S; ++k) {
-            slot[cur[first[l] + k]] = k;
-            slot[ntab[l] + S + k] = newl[first[l] + k];   // newlab after axis
-        }
-    }
-    char* dt = ctx.arena.get<char>("kdb_tables", off[n_levels] + 64);
-    PD_HIP(hipMemcpyAsync(dt, h, off[n_levels], hipMemcpyHostToDevice, s));
-    struct Lv {
-        int32_t *slot, *axis, *newlab;
-        double *bounds, *boundary;
-    };
-    std::vector<Lv> lv(n_levels);
-    for (int l = 0; l < n_levels; ++l) {
-        const int S = sizes[l];
-        lv[l].slot = (int32_t*)(dt + off[l]);
-        lv[l].axis = lv[l].slot + ntab[l];
-        lv[l].newlab = lv[l].axis + S;
-        lv[l].bounds = (double*)(dt + off_d[l]);
-        lv[l].boundary = lv[l].bounds + 7 * S;
-    }
+    KdLevels L;
+    L.layout("kd_build", n_levels, sizes, cur, newl, kTabLds);
+    const int total = L.total;
+    char* h = (char*)pinned(ctx, std::max(L.bytes(), trace_bbox_bytes(total)));
+    L.fill(h, cur, newl);
+    char* dt = ctx.arena.get<char>("kdb_tables", L.bytes() + 64);
+    PD_HIP(hipMemcpyAsync(dt, h, L.bytes(), hipMemcpyHostToDevice, s));
+    // (the pinned block is next written by read_trace_bbox's copies, ordered
+    // after this one on s)
     double* trace = ctx.arena.get<double>("kdb_trace", (size_t)total * kTrace);
     unsigned long long* dcnt = ctx.arena.get<unsigned long long>("kdb_cnt", (size_t)kTabLds * 8);
-    // Fused levels (kdf_kernel): a level of <= 2 splits whose
-    // children are exactly the next level's splits counts its candidates and
-    // sums its (split, interval) moments in one pass; the next level's
-    // moments come from those (kdb_children_kernel) and its own counting pass
-    // applies this level's split.  dst[l]: per split of level l, the slot of
-    // its left / right child in level l + 1 (-1: not split there).
-    // label replay: every level's tables in ReplayLds
-    bool replay = final_mode == 2 && ctx.kd_replay && n_levels <= kMaxLevels;
-    ReplayTab rpt;
-    {
-        int so = 0, eo = 0;
-        for (int l = 0; l < n_levels && l < kMaxLevels; ++l) {
-            rpt.ntab[l] = ntab[l];
-            rpt.nsplit[l] = sizes[l];
-            rpt.toff[l] = so;
-            rpt.eoff[l] = eo;
-            so += ntab[l];
-            eo += sizes[l];
-        }
-        replay = replay && so <= kRSlots && eo <= kRSplits;
-    }
-    std::vector<char> fuse(n_levels, 0);
-    std::vector<std::vector<int32_t>> dst(n_levels);
-    for (int l = 0; ctx.kd_fuse && !replay && l + 1 < n_levels; ++l) {
-        const int S = sizes[l], S1 = sizes[l + 1];
-        if (S > 2 || S1 > 4) continue;
-        std::vector<int32_t> dd(2 * S, -1);
-        int found = 0;
-        for (int j = 0; j < S1; ++j) {
-            const int X = cur[first[l + 1] + j];
-            for (int k = 0; k < S; ++k) {
-                if (cur[first[l] + k] == X && dd[2 * k] < 0) { dd[2 * k] = j; ++found; break; }
-                if (newl[first[l] + k] == X && dd[2 * k + 1] < 0) { dd[2 * k + 1] = j; ++found; break; }
-            }
-        }
-        if (found != S1) continue;   // a split of level l + 1 is not a child of level l
-        fuse[l] = 1;
-        dst[l] = dd;
-    }
-    int32_t* ddst = ctx.arena.get<int32_t>("kdb_dst", (size_t)n_levels * 8);
-    {
-        std::vector<int32_t> hd((size_t)n_levels * 8, -1);
-        for (int l = 0; l < n_levels; ++l)
-            for (size_t i = 0; i < dst[l].size(); ++i) hd[(size_t)l * 8 + i] = dst[l][i];
-        int32_t* hp = (int32_t*)(h + off[n_levels]);   // (the trace's block: read back only later)
-        std::memcpy(hp, hd.data(), sizeof(int32_t) * hd.size());
-        PD_HIP(hipMemcpyAsync(ddst, hp, sizeof(int32_t) * hd.size(), hipMemcpyHostToDevice, s));
-    }
-    for (int l = 0; replay && l < n_levels; ++l) {
-        rpt.slot[l] = lv[l].slot;
-        rpt.axis[l] = lv[l].axis;
-        rpt.newlab[l] = lv[l].newlab;
-        rpt.boundary[l] = lv[l].boundary;
-    }
     dispatch_t(dtype, [&](auto tp) {
         using T = std::remove_pointer_t<decltype(tp)>;
         dispatch_d(d, [&](auto Dc) {
@@ -2058,176 +1580,32 @@ void kd_build(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int32_t* lab
             const T* Xt = (const T*)X;
             double* fin0 = ctx.arena.get<double>("kdb_fin0", G + 2 * D + 1);
             double* mom = ctx.arena.get<double>("kdb_mom", (size_t)kTabLds * G);
-            double* momc = ctx.arena.get<double>("kdb_momc", (size_t)2 * 8 * G);   // children's
-            double* ifin = ctx.arena.get<double>("kdb_ifin", (size_t)2 * 8 * G);   // interval moments
             const SplitTab none{nullptr, 0, nullptr, nullptr, nullptr, 0};
             run_pass_dev<T, D, false, false, 1, true>(ctx, Xt, n, labels, none,
                                                       make_int4(cur[0], -2, -2, -2), fin0, s);
             bool labels_written = false;   // some pass wrote the labels
             for (int l = 0; l < n_levels; ++l) {
-                const int S = sizes[l];
-                const int32_t* sel = cur + first[l];
+                const KdLevel v = L.level(dt, l);
                 const double* m = fin0;
-                // this level's counting pass still has the previous split to apply
-                const bool pending = l > 0 && fuse[l - 1];
-                ReplayTab rpl = rpt;   // the levels decided so far
-                rpl.nl = l;
-                if (l > 0 && pending) {
-                    m = momc;
-                } else if (l > 0 && replay) {
-                    for (int g0 = 0; g0 < S; g0 += kGroup) {
-                        const int ng = std::min(S - g0, kGroup);
-                        int4 sl = make_int4(-2, -2, -2, -2);
-                        for (int g = 0; g < ng; ++g) (&sl.x)[g] = sel[g0 + g];
-                        dispatch_ng(ng, [&](auto NGc) {
-                            constexpr int NG = decltype(NGc)::value;
-                            run_pass_dev<T, D, false, false, NG, false, true>(
-                                ctx, Xt, n, labels, none, sl, mom + (size_t)g0 * G, s, rpl);
-                        });
-                    }
-                    m = mom;
-                } else if (l > 0) {
-                    const Lv& p = lv[l - 1];
-                    const SplitTab sp{p.slot, ntab[l - 1], p.axis, p.boundary, p.newlab, sizes[l - 1]};
-                    for (int g0 = 0; g0 < S; g0 += kGroup) {
-                        const int ng = std::min(S - g0, kGroup);
-                        int4 sl = make_int4(-2, -2, -2, -2);
-                        for (int g = 0; g < ng; ++g) (&sl.x)[g] = sel[g0 + g];
-                        dispatch_ng(ng, [&](auto NGc) {
-                            constexpr int NG = decltype(NGc)::value;
-                            if (g0 == 0 && !labels_written)   // labels all 0 so far: not read
-                                run_pass_dev<T, D, false, true, NG, false>(ctx, Xt, n, labels, sp, sl,
-                                                                           mom, s);
-                            else if (g0 == 0)
-                                run_pass_dev<T, D, true, true, NG, false>(ctx, Xt, n, labels, sp, sl,
-                                                                          mom, s);
-                            else
-                                run_pass_dev<T, D, true, false, NG, false>(
-                                    ctx, Xt, n, labels, none, sl, mom + (size_t)g0 * G, s);
-                        });
-                    }
+                if (l > 0) {
+                    level_moments<T, D>(ctx, Xt, n, labels, labels_written, L.level(dt, l - 1),
+                                        cur + v.first, v.S, mom, s);
                     labels_written = true;
                     m = mom;
                 }
-                double* tr = trace + (size_t)first[l] * kTrace;
-                hipLaunchKernelGGL(kdb_axes_kernel, dim3(1), dim3(kTabLds), 0, s, m, S, D, G,
-                                   lv[l].axis, lv[l].bounds, tr, dcnt);
-                const unsigned nb4 = grid_for((n + 3) / 4, 2048);
-                if (fuse[l] || pending) {
-                    // kdf_kernel: the previous split (pending), the counts, and
-                    // (fuse) the children's interval moments
-                    const Lv* pv = pending ? &lv[l - 1] : nullptr;
-                    const SplitTab sp = pending ? SplitTab{pv->slot, ntab[l - 1], pv->axis, pv->boundary,
-                                                           pv->newlab, sizes[l - 1]}
-                                                : none;
-                    auto go = [&](auto LABc, auto SPc, auto NSc, auto MOMc) {
-                        constexpr bool LAB_ = decltype(LABc)::value, SP_ = decltype(SPc)::value,
-                                       MOM_ = decltype(MOMc)::value;
-                        constexpr int NS_ = decltype(NSc)::value;
-                        constexpr int NW_ = (MOM_ && NS_ == 2) ? 8 : 4;
-                        constexpr int TP_ = 4 * ((sizeof(T) * D <= 16) ? 2 : 1) * 64 * NW_;
-                        static int resident = 0;
-                        if (!resident) {
-                            int per_cu = 0, dev = 0, cus = 0;
-                            PD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                                &per_cu,
-                                reinterpret_cast<const void*>(&kdf_kernel<T, D, LAB_, SP_, NS_, MOM_, NW_>),
-                                64 * NW_, 0));
-                            PD_HIP(hipGetDevice(&dev));
-                            PD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-                            resident = std::max(1, per_cu) * std::max(1, cus);
-                        }
-                        const int nb = (int)std::min<int64_t>(resident, std::max<int64_t>(1, (n + TP_ - 1) / TP_));
-                        double* part = MOM_ ? ctx.arena.get<double>("pass_part", (size_t)nb * NS_ * 8 * G)
-                                            : nullptr;
-                        hipLaunchKernelGGL((kdf_kernel<T, D, LAB_, SP_, NS_, MOM_, NW_>), dim3(nb),
-                                           dim3(64 * NW_), 0, s, Xt, (uint64_t)n, labels, sp, lv[l].slot,
-                                           ntab[l], lv[l].axis, lv[l].bounds, S, dcnt, part);
-                        PD_HIP(hipGetLastError());
-                        if constexpr (MOM_) {
-                            hipLaunchKernelGGL(kd_finish_kernel, dim3(NS_ * 8 * G), dim3(kBlock), 0, s, part, nb,
-                                               NS_ * 8 * G, G, D, NS_ * 8 * G, ifin);
-                            PD_HIP(hipGetLastError());
-                        }
-                    };
-                    using TT = std::true_type;
-                    using FF = std::false_type;
-                    auto ns = [&](auto LABc, auto SPc, auto MOMc) {
-                        if (S == 1) go(LABc, SPc, std::integral_constant<int, 1>{}, MOMc);
-                        else if (S == 2) go(LABc, SPc, std::integral_constant<int, 2>{}, MOMc);
-                        else if constexpr (!decltype(MOMc)::value)
-                            go(LABc, SPc, std::integral_constant<int, 4>{}, MOMc);
-                    };
-                    if (S > 4 || (fuse[l] && S > 2)) throw Error(-1, "kd_build: fused level too wide");
-                    if (fuse[l]) {
-                        if (!pending) ns(FF{}, FF{}, TT{});   // level 0: labels all 0, nothing to apply
-                        else if (!labels_written) ns(FF{}, TT{}, TT{});
-                        else ns(TT{}, TT{}, TT{});
-                    } else {
-                        if (!labels_written) ns(FF{}, TT{}, FF{});
-                        else ns(TT{}, TT{}, FF{});
-                    }
-                    if (pending) labels_written = true;
-                } else if (S <= 4) {
-                    auto go = [&](auto NSc) {
-                        constexpr int NS = decltype(NSc)::value;
-                        if (replay && l > 0)
-                            hipLaunchKernelGGL((counts_reg_kernel<T, D, NS, true>), dim3(nb4),
-                                               dim3(kBlock), 0, s, Xt, (uint64_t)n, nullptr,
-                                               lv[l].slot, ntab[l], lv[l].axis, lv[l].bounds, S,
-                                               dcnt, rpl);
-                        else
-                            hipLaunchKernelGGL((counts_reg_kernel<T, D, NS>), dim3(nb4), dim3(kBlock), 0,
-                                               s, Xt, (uint64_t)n, labels_written ? labels : nullptr,
-                                               lv[l].slot, ntab[l], lv[l].axis, lv[l].bounds, S, dcnt,
-                                               ReplayTab{});
-                    };
-                    if (S == 1)
-                        go(std::integral_constant<int, 1>{});
-                    else if (S == 2)
-                        go(std::integral_constant<int, 2>{});
-                    else
-                        go(std::integral_constant<int, 4>{});
-                } else {
-                    int rep = kRep;
-                    while (rep > 1 && (size_t)rep * S * 8 * sizeof(unsigned int) > 48 * 1024) rep >>= 1;
-                    hipLaunchKernelGGL((counts4_kernel<T, D>), dim3(nb4), dim3(kBlock),
-                                       sizeof(unsigned int) * rep * S * 8, s, Xt, (uint64_t)n, labels,
-                                       lv[l].slot, ntab[l], lv[l].axis, lv[l].bounds, S, 0, rep,
-                                       dcnt, replay ? rpl : ReplayTab{});
-                }
+                double* tr = trace + (size_t)v.first * kTrace;
+                hipLaunchKernelGGL(kdb_axes_kernel, dim3(1), dim3(kTabLds), 0, s, m, v.S, D, G,
+                                   v.axis, v.bounds, tr, dcnt);
+                level_counts<T, D>(Xt, n, labels, labels_written, v, dcnt, s);
+                hipLaunchKernelGGL(kdb_boundary_kernel, dim3(1), dim3(kTabLds), 0, s, dcnt, v.S,
+                                   v.bounds, v.boundary, tr);
                 PD_HIP(hipGetLastError());
-                hipLaunchKernelGGL(kdb_boundary_kernel, dim3(1), dim3(kTabLds), 0, s, dcnt, S,
-                                   lv[l].bounds, lv[l].boundary, tr);
-                PD_HIP(hipGetLastError());
-                if (fuse[l]) {
-                    hipLaunchKernelGGL(kdb_children_kernel, dim3(1), dim3(64), 0, s, ifin, S, G, tr,
-                                       ddst + (size_t)l * 8, momc);
-                    PD_HIP(hipGetLastError());
-                }
             }
             // the last level's split alone (or left to the caller: pd_train_tree
             // replays the split tree, the labels are then applied lazily)
-            if (final_split) {
-                const Lv& p = lv[n_levels - 1];
-                const SplitTab sp{p.slot, ntab[n_levels - 1], p.axis, p.boundary, p.newlab,
-                                  sizes[n_levels - 1]};
-                if (!labels_written)   // no level pass wrote the labels yet
-                    run_pass_dev<T, D, false, true, 0, false>(ctx, Xt, n, labels, sp,
-                                                              make_int4(-2, -2, -2, -2), nullptr, s);
-                else
-                    run_pass_dev<T, D, true, true, 0, false>(ctx, Xt, n, labels, sp,
-                                                             make_int4(-2, -2, -2, -2), nullptr, s);
-            }
-            // one copy back: the trace and the bbox
-            double* ht = (double*)(h + off[n_levels]);
-            PD_HIP(hipMemcpyAsync(ht, trace, sizeof(double) * total * kTrace, hipMemcpyDeviceToHost, s));
-            PD_HIP(hipMemcpyAsync(ht + (size_t)total * kTrace, fin0 + G, sizeof(double) * (2 * D + 1),
-                                  hipMemcpyDeviceToHost, s));
-            sync(s);
-            std::memcpy(trace_out, ht, sizeof(double) * total * kTrace);
-            for (int j = 0; j < 2 * D; ++j) lohi[j] = ht[(size_t)total * kTrace + j];
-            if (bad) *bad = (int64_t)ht[(size_t)total * kTrace + 2 * D];
+            if (final_split)
+                final_split_pass<T, D>(ctx, Xt, n, labels, labels_written, L.level(dt, n_levels - 1), s);
+            read_trace_bbox(ctx, trace, total, fin0 + G, D, trace_out, lohi, bad, s);
         });
     });
 }
@@ -2280,25 +1658,9 @@ __global__ void kdx_empty_kernel(double* __restrict__ out, int SG, int len, int 
     out[k] = k < SG ? 0.0 : (b < D ? INFINITY : (b < 2 * D ? -INFINITY : 0.0));
 }
 
-struct KdxLv {
-    int32_t *slot, *axis, *newlab;
-    double *bounds, *boundary;
-};
-
-KdxLv kdx_level(const KdxState& k, int l) {
-    const int S = k.sizes[l];
-    KdxLv v;
-    v.slot = (int32_t*)(k.tables + k.off[l]);
-    v.axis = v.slot + k.ntab[l];
-    v.newlab = v.axis + S;
-    v.bounds = (double*)(k.tables + k.off_d[l]);
-    v.boundary = v.bounds + 7 * S;
-    return v;
-}
-
 void kdx_check(const Ctx& ctx, int level) {
     if (!ctx.kdx.valid) throw Error(-1, "pd_kdx_*: no pd_kdx_begin on this context");
-    if (level < 0 || level >= ctx.kdx.n_levels) throw Error(-1, "pd_kdx_*: level out of range");
+    if (level < 0 || level >= ctx.kdx.lv.n_levels) throw Error(-1, "pd_kdx_*: level out of range");
 }
 }  // namespace
 
@@ -2308,44 +1670,14 @@ void kdx_begin(Ctx& ctx, int d, int n_levels, const int32_t* sizes, const int32_
     k = KdxState{};
     if (n_levels <= 0 || n_levels > 16) throw Error(-5, "pd_kdx_begin: 1..16 levels");
     if (d < 1 || d > kMaxDim) throw Error(-5, "pd_kdx_begin: d <= 4");
-    k.n_levels = n_levels;
     k.d = d;
-    k.sizes.assign(sizes, sizes + n_levels);
-    k.first.assign(n_levels, 0);
-    k.ntab.assign(n_levels, 1);
-    k.off.assign(n_levels + 1, 0);
-    k.off_d.assign(n_levels, 0);
-    int total = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        const int S = sizes[l];
-        if (S < 1 || S > kTabLds) throw Error(-5, "pd_kdx_begin: level too wide");
-        k.first[l] = total;
-        for (int q = 0; q < S; ++q) {
-            const int L = cur[total + q], N = newl[total + q];
-            if (L < 0 || L >= kTabLds || N < 0)
-                throw Error(-5, "pd_kdx_begin: labels beyond the LDS tables");
-            k.ntab[l] = std::max(k.ntab[l], L + 1);
-        }
-        const size_t ints = (size_t)k.ntab[l] + 2 * S;
-        k.off_d[l] = k.off[l] + ((sizeof(int32_t) * ints + 7) & ~size_t(7));
-        k.off[l + 1] = k.off_d[l] + sizeof(double) * 8 * S;
-        total += S;
-    }
-    k.total = total;
+    k.lv.layout("pd_kdx_begin", n_levels, sizes, cur, newl, kTabLds);
+    const int total = k.lv.total;
     k.cur.assign(cur, cur + total);
-    char* h = (char*)pinned(ctx, k.off[n_levels]);
-    std::memset(h, 0, k.off[n_levels]);
-    for (int l = 0; l < n_levels; ++l) {
-        int32_t* slot = (int32_t*)(h + k.off[l]);
-        const int S = sizes[l];
-        for (int q = 0; q < k.ntab[l]; ++q) slot[q] = -1;
-        for (int q = 0; q < S; ++q) {
-            slot[cur[k.first[l] + q]] = q;
-            slot[k.ntab[l] + S + q] = newl[k.first[l] + q];
-        }
-    }
-    k.tables = ctx.arena.get<char>("kdx_tables", k.off[n_levels] + 64);
-    PD_HIP(hipMemcpyAsync(k.tables, h, k.off[n_levels], hipMemcpyHostToDevice, s));
+    char* h = (char*)pinned(ctx, k.lv.bytes());
+    k.lv.fill(h, cur, newl);
+    k.tables = ctx.arena.get<char>("kdx_tables", k.lv.bytes() + 64);
+    PD_HIP(hipMemcpyAsync(k.tables, h, k.lv.bytes(), hipMemcpyHostToDevice, s));
     sync(s);   // the pinned block is reused by later calls
     k.trace = ctx.arena.get<double>("kdx_trace", (size_t)total * kTrace);
     k.bbox = ctx.arena.get<double>("kdx_bbox", 2 * kMaxDim + 1);
@@ -2358,7 +1690,7 @@ void kdx_moments(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int32_t* 
     kdx_check(ctx, level);
     const KdxState& k = ctx.kdx;
     if (d != k.d) throw Error(-1, "pd_kdx_moments: d differs from pd_kdx_begin");
-    const int S = k.sizes[level], G = 1 + 4 * d;
+    const int S = k.lv.sizes[level], G = 1 + 4 * d;
     const int len = S * G + (level == 0 ? 2 * d + 1 : 0);
     if (n == 0) {
         hipLaunchKernelGGL(kdx_empty_kernel, dim3((len + 255) / 256), dim3(256), 0, s, out, S * G,
@@ -2368,35 +1700,20 @@ void kdx_moments(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int32_t* 
     }
     if (ctx.seq_moments || !vec_ok(d, X, labels))
         throw Error(-5, "pd_kdx_moments: d <= 4, 16-byte aligned inputs and exact sums only");
-    const int32_t* sel = k.cur.data() + k.first[level];
+    const int32_t* sel = k.cur.data() + k.lv.first[level];
     dispatch_t(dtype, [&](auto tp) {
         using T = std::remove_pointer_t<decltype(tp)>;
         dispatch_d(d, [&](auto Dc) {
             constexpr int D = decltype(Dc)::value;
-            constexpr int Gc = 1 + 4 * D;
             const T* Xt = (const T*)X;
-            const SplitTab none{nullptr, 0, nullptr, nullptr, nullptr, 0};
             if (level == 0) {   // bbox + the root's moments, labels not read
+                const SplitTab none{nullptr, 0, nullptr, nullptr, nullptr, 0};
                 run_pass_dev<T, D, false, false, 1, true>(ctx, Xt, n, labels, none,
                                                           make_int4(sel[0], -2, -2, -2), out, s);
                 return;
             }
-            const KdxLv p = kdx_level(k, level - 1);
-            const SplitTab sp{p.slot, k.ntab[level - 1], p.axis, p.boundary, p.newlab,
-                              k.sizes[level - 1]};
-            for (int g0 = 0; g0 < S; g0 += kGroup) {
-                const int ng = std::min(S - g0, kGroup);
-                int4 sl = make_int4(-2, -2, -2, -2);
-                for (int g = 0; g < ng; ++g) (&sl.x)[g] = sel[g0 + g];
-                dispatch_ng(ng, [&](auto NGc) {
-                    constexpr int NG = decltype(NGc)::value;
-                    if (g0 == 0)
-                        run_pass_dev<T, D, true, true, NG, false>(ctx, Xt, n, labels, sp, sl, out, s);
-                    else
-                        run_pass_dev<T, D, true, false, NG, false>(ctx, Xt, n, labels, none, sl,
-                                                                   out + (size_t)g0 * Gc, s);
-                });
-            }
+            level_moments<T, D>(ctx, Xt, n, labels, true, k.lv.level(k.tables, level - 1), sel, S,
+                                out, s);
         });
     });
 }
@@ -2405,13 +1722,13 @@ void kdx_axes(Ctx& ctx, const double* gathered, int n_ranks, int level, hipStrea
     kdx_check(ctx, level);
     const KdxState& k = ctx.kdx;
     if (n_ranks < 1) throw Error(-1, "pd_kdx_axes: n_ranks < 1");
-    const int d = k.d, S = k.sizes[level], G = 1 + 4 * d;
+    const KdLevel v = k.lv.level(k.tables, level);
+    const int d = k.d, S = v.S, G = 1 + 4 * d;
     const int len = S * G + (level == 0 ? 2 * d + 1 : 0);
     hipLaunchKernelGGL(kdx_combine_kernel, dim3((len + 255) / 256), dim3(256), 0, s, gathered,
                        n_ranks, len, S * G, G, d, k.mom, k.bbox);
-    const KdxLv v = kdx_level(k, level);
     hipLaunchKernelGGL(kdb_axes_kernel, dim3(1), dim3(kTabLds), 0, s, k.mom, S, d, G, v.axis,
-                       v.bounds, k.trace + (size_t)k.first[level] * kTrace,
+                       v.bounds, k.trace + (size_t)v.first * kTrace,
                        (unsigned long long*)nullptr);
     PD_HIP(hipGetLastError());
 }
@@ -2420,48 +1737,25 @@ void kdx_counts(Ctx& ctx, const void* X, int dtype, int64_t n, int d, const int3
                 int level, unsigned long long* out, hipStream_t s) {
     kdx_check(ctx, level);
     const KdxState& k = ctx.kdx;
-    const int S = k.sizes[level];
-    PD_HIP(hipMemsetAsync(out, 0, sizeof(unsigned long long) * S * 8, s));
+    const KdLevel v = k.lv.level(k.tables, level);
+    PD_HIP(hipMemsetAsync(out, 0, sizeof(unsigned long long) * v.S * 8, s));
     if (n == 0) return;
     if (!vec_ok(d, X, labels)) throw Error(-5, "pd_kdx_counts: 16-byte aligned inputs only");
-    const KdxLv v = kdx_level(k, level);
     dispatch_t(dtype, [&](auto tp) {
         using T = std::remove_pointer_t<decltype(tp)>;
         dispatch_d(d, [&](auto Dc) {
             constexpr int D = decltype(Dc)::value;
-            const T* Xt = (const T*)X;
-            const unsigned nb4 = grid_for((n + 3) / 4, 2048);
-            if (S <= 4) {
-                auto go = [&](auto NSc) {
-                    constexpr int NS = decltype(NSc)::value;
-                    hipLaunchKernelGGL((counts_reg_kernel<T, D, NS>), dim3(nb4), dim3(kBlock), 0, s,
-                                       Xt, (uint64_t)n, labels, v.slot, k.ntab[level], v.axis,
-                                       v.bounds, S, out, ReplayTab{});
-                };
-                if (S == 1)
-                    go(std::integral_constant<int, 1>{});
-                else if (S == 2)
-                    go(std::integral_constant<int, 2>{});
-                else
-                    go(std::integral_constant<int, 4>{});
-            } else {
-                int rep = kRep;
-                while (rep > 1 && (size_t)rep * S * 8 * sizeof(unsigned int) > 48 * 1024) rep >>= 1;
-                hipLaunchKernelGGL((counts4_kernel<T, D>), dim3(nb4), dim3(kBlock),
-                                   sizeof(unsigned int) * rep * S * 8, s, Xt, (uint64_t)n, labels,
-                                   v.slot, k.ntab[level], v.axis, v.bounds, S, 0, rep, out, ReplayTab{});
-            }
+            level_counts<T, D>((const T*)X, n, labels, true, v, out, s);
         });
     });
-    PD_HIP(hipGetLastError());
 }
 
 void kdx_boundary(Ctx& ctx, const unsigned long long* cnt, int level, hipStream_t s) {
     kdx_check(ctx, level);
     const KdxState& k = ctx.kdx;
-    const KdxLv v = kdx_level(k, level);
-    hipLaunchKernelGGL(kdb_boundary_kernel, dim3(1), dim3(kTabLds), 0, s, cnt, k.sizes[level],
-                       v.bounds, v.boundary, k.trace + (size_t)k.first[level] * kTrace);
+    const KdLevel v = k.lv.level(k.tables, level);
+    hipLaunchKernelGGL(kdb_boundary_kernel, dim3(1), dim3(kTabLds), 0, s, cnt, v.S, v.bounds,
+                       v.boundary, k.trace + (size_t)v.first * kTrace);
     PD_HIP(hipGetLastError());
 }
 
@@ -2470,28 +1764,18 @@ void kdx_end(Ctx& ctx, const void* X, int dtype, int64_t n, int d, int32_t* labe
     KdxState& k = ctx.kdx;
     if (!k.valid) throw Error(-1, "pd_kdx_end: no pd_kdx_begin on this context");
     if (d != k.d) throw Error(-1, "pd_kdx_end: d differs from pd_kdx_begin");
-    const int nl = k.n_levels;
     if (final_split && n > 0) {
         if (!vec_ok(d, X, labels)) throw Error(-5, "pd_kdx_end: 16-byte aligned inputs only");
-        const KdxLv p = kdx_level(k, nl - 1);
-        const SplitTab sp{p.slot, k.ntab[nl - 1], p.axis, p.boundary, p.newlab, k.sizes[nl - 1]};
+        const KdLevel last = k.lv.level(k.tables, k.lv.n_levels - 1);
         dispatch_t(dtype, [&](auto tp) {
             using T = std::remove_pointer_t<decltype(tp)>;
             dispatch_d(d, [&](auto Dc) {
                 constexpr int D = decltype(Dc)::value;
-                run_pass_dev<T, D, true, true, 0, false>(ctx, (const T*)X, n, labels, sp,
-                                                         make_int4(-2, -2, -2, -2), nullptr, s);
+                final_split_pass<T, D>(ctx, (const T*)X, n, labels, true, last, s);
             });
         });
     }
-    double* h = (double*)pinned(ctx, sizeof(double) * ((size_t)k.total * kTrace + 2 * kMaxDim + 8));
-    PD_HIP(hipMemcpyAsync(h, k.trace, sizeof(double) * k.total * kTrace, hipMemcpyDeviceToHost, s));
-    PD_HIP(hipMemcpyAsync(h + (size_t)k.total * kTrace, k.bbox, sizeof(double) * (2 * d + 1),
-                          hipMemcpyDeviceToHost, s));
-    sync(s);
-    std::memcpy(trace_out, h, sizeof(double) * k.total * kTrace);
-    for (int j = 0; j < 2 * d; ++j) lohi[j] = h[(size_t)k.total * kTrace + j];
-    if (bad) *bad = (int64_t)h[(size_t)k.total * kTrace + 2 * d];
+    read_trace_bbox(ctx, k.trace, k.lv.total, k.bbox, d, trace_out, lohi, bad, s);
     k.valid = false;
 }
 

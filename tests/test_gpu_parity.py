@@ -306,8 +306,9 @@ def test_sweeps_exact(native, stats):
 
 
 def test_retired_options_raise(native):
-    """The tuning knobs retired in round 5 (their losing kernels are gone)
-    are refused, not silently ignored."""
+    """The tuning knobs retired after rounds 5 and 6 (their losing kernels are
+    gone; PD_OPT_RETIRED lists 4, 5, 9, 10, 16, 20-23, 27, 29 and 30) are refused,
+    not silently ignored."""
     ctx = native.context()
     for opt in native.PD_OPT_RETIRED:
         with pytest.raises(native.PardisError):
@@ -1140,41 +1141,23 @@ def _kd_case(name):
 def test_kd_device_decisions_equal_host(native, name, P):
     """pd_kd_build (level decisions on the device, one sync) gives the per-pass
     host-decided path's split trace, boxes and labels bit for bit — levels of
-    1..128 splits, fp32 / fp64, zero variance, fewer points than partitions —
-    without the fused levels (the default), with them (PD_OPT_KD_FUSE:
-    counts + the children's interval moments in one pass) and with the
-    labels replayed from the split tree instead of kept in HBM
-    (PD_OPT_KD_REPLAY)."""
+    1..128 splits, fp32 / fp64, zero variance, fewer points than partitions."""
     from pypardis_amd import KDPartitioner, partition
     X = _kd_case(name)
     Xd = _dev(X)
     a = KDPartitioner(Xd, P)
-    ctx = native.context()
-    ctx.set_option(native.PD_OPT_KD_FUSE, 1)
-    try:
-        c = KDPartitioner(Xd, P)
-    finally:
-        ctx.set_option(native.PD_OPT_KD_FUSE, 0)
-    ctx.set_option(native.PD_OPT_KD_REPLAY, 1)
-    try:
-        r = KDPartitioner(Xd, P)
-        r.labels   # (replayed now, under the option)
-    finally:
-        ctx.set_option(native.PD_OPT_KD_REPLAY, 0)
     partition.DEVICE_DECISIONS = False
     try:
         b = KDPartitioner(Xd, P)
     finally:
         partition.DEVICE_DECISIONS = True
-    sb, fb = _kd_arrays(b.splits)
-    for m in (a, c, r):
-        sa, fa = _kd_arrays(m.splits)
-        assert np.array_equal(sa, sb)
-        assert np.array_equal(fa, fb, equal_nan=True)
-        assert np.array_equal(m.box_array(), b.box_array(), equal_nan=True)
-        assert torch.equal(m.labels, b.labels)
-        assert m.data_box[0].tolist() == b.data_box[0].tolist()
     sa, fa = _kd_arrays(a.splits)
+    sb, fb = _kd_arrays(b.splits)
+    assert np.array_equal(sa, sb)
+    assert np.array_equal(fa, fb, equal_nan=True)
+    assert np.array_equal(a.box_array(), b.box_array(), equal_nan=True)
+    assert torch.equal(a.labels, b.labels)
+    assert a.data_box[0].tolist() == b.data_box[0].tolist()
     if name == "c2_1m" and P == 8:   # and the oracle's exact restatement
         ref = oracle.kd_partition(X, P, sums="exact")
         assert np.array_equal(sa, _kd_arrays(ref["splits"])[0])
@@ -1241,18 +1224,17 @@ def test_halo_single_pass_equals_two_pass(native, P, cap):
         assert m.n_clusters_ == nc_o
 
 
-HALO_TREE = [("c2", 8), ("c2", 64), ("c4", 8), ("c4", 37), ("lattice", 16), ("f64_4d", 13),
-             ("dup", 8), ("city", 5)]
+HALO_CASES = [("c2", 8), ("c2", 64), ("c4", 8), ("c4", 37), ("lattice", 16), ("f64_4d", 13),
+              ("dup", 8), ("city", 5)]
 
 
-@pytest.mark.parametrize("case,P", HALO_TREE, ids=[f"{c}-P{p}" for c, p in HALO_TREE])
-def test_halo_tree_equals_full_test(native, case, P):
-    """PD_OPT_HALO_TREE (opt-in, measured slower): the halo's near-plane path — a
-    point farther than 2 eps from every split plane on its KD path gets its
-    owner's record only, the rest the full box test — writes the records of
-    the full test (same count) and gives the oracle's labels: 2-D / 3-D / 4-D,
-    fp32 / fp64, lattice points exactly on split planes, duplicates, cityblock,
-    up to 64 partitions."""
+@pytest.mark.parametrize("case,P", HALO_CASES, ids=[f"{c}-P{p}" for c, p in HALO_CASES])
+def test_halo_split_tree_train_matches_oracle(native, case, P):
+    """DBSCAN.train with the split tree replayed in the halo pass (P <= 64: the
+    tree in LDS) gives the oracle's labels, core flags and cluster count, and
+    one record per (point, expanded box) membership: 2-D / 3-D / 4-D, fp32 /
+    fp64, lattice points exactly on split planes, duplicates, cityblock, up
+    to 64 partitions."""
     from pypardis_amd import DBSCAN, synth
     rng = np.random.default_rng(P)
     metric, eps, ms = "euclidean", 0.1, 10
@@ -1279,19 +1261,15 @@ def test_halo_tree_equals_full_test(native, case, P):
     lab_o, core_o, _, nc_o = oracle.dbscan(X, eps, ms, metric)
     ctx = native.context()
     Xd = _dev(X)
-    out = []
-    for on in (1, 0):
-        ctx.set_option(native.PD_OPT_HALO_TREE, on)
-        try:
-            m = DBSCAN(eps=eps, min_samples=ms, metric=metric, max_partitions=P).train(Xd)
-        finally:
-            ctx.set_option(native.PD_OPT_HALO_TREE, 0)
-        out.append((m, int(ctx.timings()["records"])))
-    assert out[0][1] == out[1][1]
-    for m, _ in out:
-        assert np.array_equal(m.labels_.cpu().numpy().astype(np.int64), lab_o)
-        assert np.array_equal(m.core_sample_mask_.cpu().numpy(), core_o)
-        assert m.n_clusters_ == nc_o
+    m = DBSCAN(eps=eps, min_samples=ms, metric=metric, max_partitions=P).train(Xd)
+    R = int(ctx.timings()["records"])
+    assert m.partitioner.split_tree() is not None
+    ebox = np.array([m.expanded_boxes[L].as_array() for L in sorted(m.expanded_boxes)], np.float64)
+    counts, _ = native.halo_members(Xd, ebox)
+    assert R == int(np.sum(counts))
+    assert np.array_equal(m.labels_.cpu().numpy().astype(np.int64), lab_o)
+    assert np.array_equal(m.core_sample_mask_.cpu().numpy(), core_o)
+    assert m.n_clusters_ == nc_o
 
 
 @pytest.mark.parametrize("cfg,n", [("C2", 2_000_000), ("C4", 3_000_000), ("C1", 500_000)])
@@ -1313,6 +1291,69 @@ def test_verify_fused_equals_listed(native, cfg, n):
         outs.append((m.labels_.clone(), m.core_sample_mask_.clone(), m.n_clusters_))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert outs[0][2] == outs[1][2]
+
+
+TREE_OWNER = [(d, dt, P) for d in (1, 2, 3, 4) for dt in (np.float32, np.float64)
+              for P in (2, 8, 64, 65, 300)]
+
+
+@pytest.fixture(scope="module")
+def tree_owner_points():
+    """3 000 points (three 1 024-point halo tiles, the last partial) on the
+    0.25 lattice in [0, 10)^d: many coordinates tie with a split boundary; the
+    oracle's answer per (d, dtype), computed once."""
+    cache = {}
+
+    def get(d, dtype):
+        if (d, dtype) not in cache:
+            rng = np.random.default_rng(100 + d)
+            X = (0.25 * rng.integers(0, 40, size=(3000, d))).astype(dtype)
+            cache[(d, dtype)] = (X, oracle.dbscan(X, 0.3, 4))
+        return cache[(d, dtype)]
+    return get
+
+
+@pytest.mark.parametrize("d,dtype,P", TREE_OWNER,
+                         ids=[f"d{d}-{np.dtype(t).name}-P{P}" for d, t, P in TREE_OWNER])
+def test_tree_owner_equals_kd_labels(native, tree_owner_points, d, dtype, P):
+    """The halo pass's owner of a point (the split tree replayed per point,
+    pd_train_tree) is the label pd_kd_labels gives it: the train with the tree
+    and the train with the replayed labels as owners are identical — labels,
+    core flags, counts, cluster count and halo records — and the oracle's.
+    Lattice coordinates tie with the boundaries of v[axis] >= bound; P <= 64
+    stages the tree in LDS (masked kernel), P > 64 reads it from global
+    memory (unmasked kernel)."""
+    from pypardis_amd import KDPartitioner
+    X, (lab_o, core_o, cnt_o, nc_o) = tree_owner_points(d, dtype)
+    Xd = _dev(X)
+    eps, ms = 0.3, 4
+    parts = KDPartitioner(Xd, P)
+    tree = parts.split_tree()
+    assert tree is not None
+    ebox = np.array([parts.bounding_boxes[L].expand(2 * eps).as_array()
+                     for L in sorted(parts.bounding_boxes)], np.float64)
+    lo, hi = parts.data_box
+    dbox = np.stack([lo, hi])
+    ctx = native.context()
+    ctx.set_option(native.PD_OPT_TIMING, 1)
+    ctx.set_option(native.PD_OPT_FULL_COUNTS, 1)   # (counts comparable with the oracle's)
+    try:
+        a = native.train_tree(Xd, eps, ms, native.PD_EUCLIDEAN, ebox, tree, data_box=dbox,
+                              want_counts=True)
+        ra = int(ctx.timings()["records"])
+        b = native.train(Xd, eps, ms, native.PD_EUCLIDEAN, ebox, owner=parts.labels,
+                         data_box=dbox, want_counts=True)
+        rb = int(ctx.timings()["records"])
+    finally:
+        ctx.set_option(native.PD_OPT_TIMING, 0)
+        ctx.set_option(native.PD_OPT_FULL_COUNTS, 0)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
+    assert a[3] == b[3] and ra == rb
+    for lab, core, cnt, ncl in (a, b):
+        assert np.array_equal(lab.cpu().numpy().astype(np.int64), lab_o)
+        assert np.array_equal(core.cpu().numpy(), core_o)
+        assert np.array_equal(cnt.cpu().numpy().astype(np.int64), cnt_o)
+        assert ncl == nc_o
 
 
 @pytest.mark.parametrize("cfg,n", [("C2", 2_000_000), ("C4", 3_000_000), ("C1", 500_000)])
