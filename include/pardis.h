@@ -116,14 +116,6 @@ enum pd_option {
                                 same values) and put its time in PD_T_COUNT_KERNEL — on a record
                                 set small enough to stay in L2, the sweep's latency ceiling.
                                 Default 0 (off) */,
-    PD_OPT_HALO_PASSES = 25   /* grid train halo records: 2 (default) tile counts, scan, write
-                                (two reads of the points); 1: one pass — each tile counts its
-                                records, takes its offset by decoupled look-back and writes them
-                                into buffers of a guessed capacity (a larger total reruns 2);
-                                measured slower on C2 (halo 1.62 vs 1.31 ms), kept for A/B.
-                                Same records either way */,
-    PD_OPT_HALO_CAP = 26      /* single-pass halo record capacity (tests: force the overflow
-                                path); 0 (default): n + n/8 + 4096 */,
     PD_OPT_VERIFY_FUSED = 28  /* link stage cell verify: 0 (default) a screen pass flags the cells
                                 whose forward rows hold another root, then the flagged cells are
                                 listed and verified; 1: one pass over every cell with the screen
@@ -135,9 +127,9 @@ enum pd_option {
        reused): 4 LINK_MODE, 5 JUMP_ROUNDS, 9 SWEEP_VARIANT, 10 BORDER_ROOTS,
        16 SORT_PAYLOAD, 20 BORDER_LISTS, 21 LINK_JUMPS, 22 DENSE_PREFETCH,
        23 DENSE_WAVES.
-       Retired after round 6 (that round's A/Bs that lost, likewise): 27
-       KD_FUSE, 29 HALO_TREE, 30 KD_REPLAY.  DESIGN.md §6 keeps the
-       measurements of both rounds. */
+       Retired after round 6 (that round's A/Bs that lost, likewise): 25
+       HALO_PASSES, 26 HALO_CAP, 27 KD_FUSE, 29 HALO_TREE, 30 KD_REPLAY.
+       DESIGN.md §6 keeps the measurements of both rounds. */
 };
 
 /* pd_ctx_timings() slots (ms from HIP events on the call's stream; counters) */
@@ -156,8 +148,7 @@ enum pd_timing_slot {
     PD_T_DIR_WORDS,            /* directory words it allocated (paged: occupied + 1) */
     PD_T_S_COUNT_BATCHES,      /* count sweep (PD_OPT_SWEEP_STATS): wave batches swept */
     PD_T_S_COUNT_STAGED,       /*   (retired LDS-staged count sweep: always 0) */
-    PD_T_HALO_FALLBACK,        /* 1 if the last single-pass halo overflowed its capacity and
-                                  the two-pass form ran */
+    PD_T_HALO_FALLBACK,        /*   (retired single-pass halo: always 0) */
     PD_T_NSLOTS
 };
 

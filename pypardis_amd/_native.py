@@ -31,15 +31,15 @@ PD_OPT_DIR_PAGED = 17
 PD_OPT_DENSE_SCREEN = 18
 PD_OPT_SHARD_CORE_BIT = 19
 PD_OPT_COUNT_REPLAY = 24
-PD_OPT_HALO_PASSES = 25
-PD_OPT_HALO_CAP = 26
 PD_OPT_VERIFY_FUSED = 28
 # retired round-6 A/B options (the names stay for tools that list them)
+PD_OPT_HALO_PASSES = 25
+PD_OPT_HALO_CAP = 26
 PD_OPT_KD_FUSE = 27
 PD_OPT_HALO_TREE = 29
 PD_OPT_KD_REPLAY = 30
 # retired after rounds 5 and 6 (pardis.h): set_option raises for them
-PD_OPT_RETIRED = (4, 5, 9, 10, 16, 20, 21, 22, 23, 27, 29, 30)
+PD_OPT_RETIRED = (4, 5, 9, 10, 16, 20, 21, 22, 23, 25, 26, 27, 29, 30)
 TIMING_SLOTS = ["halo", "sort", "gather", "cells", "count", "link", "merge", "roots", "border",
                 "label", "total", "records", "cells_n", "grid_cells", "key_bits", "core_records",
                 "s_count_cand", "s_link_cand", "s_link_hit", "s_link_core", "s_link_same",

@@ -168,19 +168,14 @@ int32_t pd_ctx_set_option(pd_ctx* ctx, int32_t option, int64_t value) {
             ctx->c.dense_screen = (int)value;
         } else if (option == PD_OPT_SHARD_CORE_BIT) {
             ctx->c.shard_core_bit = value != 0;
-        } else if (option == PD_OPT_HALO_PASSES) {
-            if (value != 1 && value != 2) throw Error(PD_EINVAL, "halo passes is 1 or 2");
-            ctx->c.halo_passes = (int)value;
         } else if (option == PD_OPT_VERIFY_FUSED) {
             ctx->c.verify_fused = value != 0;
-        } else if (option == PD_OPT_HALO_CAP) {
-            if (value < 0) throw Error(PD_EINVAL, "halo capacity must be >= 0");
-            ctx->c.halo_cap = value;
         } else if (option == PD_OPT_COUNT_REPLAY) {
             if (value < 0 || value > 65536) throw Error(PD_EINVAL, "count replay must be in [0, 65536]");
             ctx->c.count_replay = (int)value;
         } else if (option == 4 || option == 5 || option == 9 || option == 10 || option == 16 ||
-                   (option >= 20 && option <= 23) || option == 27 || option == 29 || option == 30) {
+                   (option >= 20 && option <= 23) || (option >= 25 && option <= 27) || option == 29 ||
+                   option == 30) {
             // retired tuning knobs (rounds 5 and 6): measured A/Bs whose
             // losing kernels were removed; pardis.h lists them
             throw Error(PD_EINVAL, "option " + std::to_string(option) +

@@ -452,9 +452,10 @@ __device__ __forceinline__ K key_of(const T (&tv)[D], const KeyGrid<D>& g) {
 // stores are contiguous; the extra records of the few halo duplicates follow.
 // (92 VGPRs, 5 waves/SIMD: capping it at 6 or 8 waves measured slower — C2
 // halo 1.29 / 1.81 vs 1.22 ms, the cap spills the per-point state)
-// Every record store is bounded by `cap` (the buffers' length): the
-// single-pass form writes before it knows the total, and a tile past the
-// capacity must not store (the host then reruns the two-pass form).
+// Every record store is bounded by `cap`, the record total of the tile scan
+// (the buffers' length): halo_tile_kernel and halo_write_kernel run the same
+// halo_points over the same input, so the offsets never reach it and the
+// guard is a backstop that costs one compare.
 // split-tree tables up to this size are staged in LDS (halo_stage, P <= 64)
 constexpr int kTreeSlots = 256, kTreeSplits = 128;
 template <int D>
@@ -511,7 +512,7 @@ __device__ __forceinline__ bool halo_stage(HaloLds<D>& L, const PartGrid* __rest
 }
 
 // write the records of one tile's points from record offset wbase (this
-// wave's first record); stores at or past cap are dropped
+// wave's first record); a store at or past cap (never, see above) is dropped
 template <typename T, int D, typename K, bool MASK>
 __device__ __forceinline__ void halo_emit(const HaloLds<D>& L, const PartGrid* __restrict__ parts,
                                           int P, const int32_t* __restrict__ owner,
@@ -579,90 +580,6 @@ __global__ __launch_bounds__(kBlock) void halo_write_kernel(
     if (lane == 0) L.ws[w] = wtot;
     __syncthreads();
     uint64_t wbase = tile_off[blockIdx.x];
-#pragma unroll
-    for (int u = 0; u < kBlock / 64; ++u) wbase += u < w ? L.ws[u] : 0u;
-    halo_emit<T, D, K, MASK>(L, parts, P, owner, tree, tree_lds, n, idx, v, m, cnt, ex, wbase, cap,
-                             keys, vals);
-}
-
-// Single-pass halo (PD_OPT_HALO_PASSES = 1): each tile counts its records,
-// learns the records of the tiles before it by decoupled look-back, and
-// writes them — one read of the points instead of two, no scan, at the price
-// of buffers sized before the total is known (cap; the host reruns the
-// two-pass form when the total passes it).  Tiles take their index from a
-// ticket (atomicAdd - tick0), so the tiles a tile waits for were dispatched
-// before it: forward progress without assuming a dispatch order.  Look-back
-// words: tag << 32 | records (tag 2 epoch + 1: the tile's own count, 2 epoch
-// + 2: inclusive of every tile before; older epochs' tags read as
-// unpublished); counts saturate at 2^32 - 1, far past any capacity.  The
-// last tile writes the total (64-bit) for the host.  Tile 0 zeroes the
-// train's counters and the sort histograms (the tile kernel's job in the
-// two-pass form).
-template <typename T, int D, typename K, bool MASK>
-__global__ __launch_bounds__(kBlock) void halo1_kernel(
-    const T* __restrict__ X, uint64_t n, const PartGrid* __restrict__ parts, int P,
-    const int32_t* __restrict__ owner, KdTree tree, uint64_t cap, K* __restrict__ keys,
-    uint32_t* __restrict__ vals, uint64_t* __restrict__ look, uint32_t epoch,
-    unsigned long long* __restrict__ ticket, unsigned long long tick0, uint32_t ntiles,
-    unsigned long long* __restrict__ total, uint32_t* __restrict__ ctrs,
-    uint32_t* __restrict__ sort_hist) {
-    __shared__ HaloLds<D> L;
-    __shared__ uint32_t s_tile;
-    __shared__ unsigned long long s_base;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_tile = (uint32_t)(atomicAdd(ticket, 1ull) - tick0);
-    const bool tree_lds = halo_stage<T, D, MASK>(L, parts, P, tree);
-    __syncthreads();
-    const uint32_t tile = s_tile;
-    if (!PD_OK(tile < ntiles, 7, tile)) return;   // (a ticket past the grid: never)
-    if (tile == 0) {
-        if (threadIdx.x < kCtrs) ctrs[threadIdx.x] = 0;
-        if (sort_hist)
-            for (int i = threadIdx.x; i < 8 * rsort::kRadix; i += kBlock) sort_hist[i] = 0;
-    }
-    uint64_t idx[4];
-    T v[4][D];
-    unsigned long long m[4];
-    uint32_t cnt[4], ex[4];
-    halo_points<T, D, MASK>(X, n, parts, P, tile, idx, v, m, cnt);
-    const uint32_t wtot = wave_offsets<4>(cnt, ex);
-    if (lane == 0) L.ws[w] = wtot;
-    __syncthreads();
-    if (w == 0) {
-        uint32_t t = 0;
-#pragma unroll
-        for (int u = 0; u < kBlock / 64; ++u) t += L.ws[u];
-        const uint32_t agg = 2u * epoch + 1u, inc = 2u * epoch + 2u;
-        if (lane == 0) rsort::st_lb(look + tile, ((uint64_t)(tile == 0 ? inc : agg) << 32) | t);
-        uint64_t excl = 0;
-        // look back 64 tiles at a time: lane l reads tile (front - l); the
-        // nearest inclusive word ends the walk, every word up to it must be
-        // published (else spin)
-        for (int64_t front = (int64_t)tile - 1; front >= 0;) {
-            const int64_t tt = front - lane;
-            const uint64_t wv = tt >= 0 ? rsort::ld_lb(look + tt) : ((uint64_t)inc << 32);
-            const uint32_t tag = (uint32_t)(wv >> 32);
-            const unsigned long long pub = __ballot(tag == agg || tag == inc);
-            const unsigned long long incl = __ballot(tag == inc);
-            const int stop = incl ? __ffsll((long long)incl) - 1 : 63;
-            const unsigned long long need = stop == 63 ? ~0ull : ((2ull << stop) - 1ull);
-            if ((pub & need) != need) continue;   // a tile up to `stop` not published yet
-            uint64_t x = lane <= stop ? (uint32_t)wv : 0u;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) x += (uint64_t)__shfl_xor((long long)x, o, 64);
-            excl += x;
-            if (incl) break;
-            front -= 64;
-        }
-        if (lane == 0) {
-            const uint64_t it = excl + t;
-            if (tile > 0) rsort::st_lb(look + tile, ((uint64_t)inc << 32) | (it < 0xFFFFFFFFull ? it : 0xFFFFFFFFull));
-            if (tile == ntiles - 1) *total = it;
-            s_base = excl;
-        }
-    }
-    __syncthreads();
-    uint64_t wbase = s_base;
 #pragma unroll
     for (int u = 0; u < kBlock / 64; ++u) wbase += u < w ? L.ws[u] : 0u;
     halo_emit<T, D, K, MASK>(L, parts, P, owner, tree, tree_lds, n, idx, v, m, cnt, ex, wbase, cap,
@@ -2836,77 +2753,27 @@ void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t
     const unsigned htiles = (unsigned)std::max<uint64_t>(1, (n + 4 * kBlock - 1) / (4 * kBlock));
     uint32_t* ctrs = ctx.arena.get<uint32_t>("train_ctrs", kCtrs);
     uint32_t* sort_hist = PD_SORT_ROCPRIM ? nullptr : ctx.arena.get<uint32_t>("rsort_hist", 8 * rsort::kRadix);
-    uint64_t R64 = ~0ull;
-    K *keys = nullptr, *keys2 = nullptr;
-    uint32_t *vals = nullptr, *vals2 = nullptr;
-    ctx.t.halo_fallback = 0;
-    if (ctx.halo_passes == 1) {
-        // single pass into buffers of a guessed capacity: n/8 + 4096 records
-        // of halo copies (the BASELINE configs duplicate 0.004-1 % at full
-        // size), or 5 % over the last train's records per point when that was
-        // more (small sets / many partitions duplicate more); a total past it
-        // reruns the two-pass form below
-        const double grow = std::max(1.125, 1.05 * ctx.h1_ratio);
-        const uint64_t cap = std::min<uint64_t>(
-            ctx.halo_cap > 0 ? (uint64_t)ctx.halo_cap : (uint64_t)(grow * (double)n) + 4096,
-            0xFFFFFFFDull);
-        keys = ctx.arena.get<K>("keys", cap);
-        vals = ctx.arena.get<uint32_t>("vals", cap);
-        uint64_t* look = ctx.arena.get<uint64_t>("halo_look", htiles);
-        auto* tick = ctx.arena.get<unsigned long long>("halo_ticket", 2);   // [0] ticket, [1] total
-        if (look != ctx.h1_look || htiles > ctx.h1_look_tiles || tick != ctx.h1_tick ||
-            ctx.h1_epoch >= 0x7FFFFFF0u) {   // new words: zero them once
-            PD_HIP(hipMemsetAsync(look, 0, sizeof(uint64_t) * htiles, s));
-            PD_HIP(hipMemsetAsync(tick, 0, sizeof(unsigned long long) * 2, s));
-            ctx.h1_look = look;
-            ctx.h1_look_tiles = htiles;
-            ctx.h1_tick = tick;
-            ctx.h1_epoch = 0;
-            ctx.h1_tick0 = 0;
-        }
-        const uint32_t ep = ctx.h1_epoch++;
-        const unsigned long long t0 = ctx.h1_tick0;
-        ctx.h1_tick0 += htiles;
-        if (P <= 64)
-            hipLaunchKernelGGL((halo1_kernel<T, D, K, true>), dim3(htiles), dim3(kBlock), 0, s, X, n,
-                               parts, P, a.owner, tree, cap, keys, vals, look, ep, tick, t0,
-                               htiles, tick + 1, ctrs, sort_hist);
-        else
-            hipLaunchKernelGGL((halo1_kernel<T, D, K, false>), dim3(htiles), dim3(kBlock), 0, s, X,
-                               n, parts, P, a.owner, tree, cap, keys, vals, look, ep, tick, t0,
-                               htiles, tick + 1, ctrs, sort_hist);
-        PD_HIP(hipGetLastError());
-        check_bounds(s, "halo1_kernel");
-        uint64_t* h = (uint64_t*)pinned(ctx, sizeof(uint64_t));
-        PD_HIP(hipMemcpyAsync(h, tick + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        sync(s);
-        if (*h <= cap) R64 = *h;
-        ctx.t.halo_fallback = R64 == ~0ull ? 1 : 0;
-    }
-    if (R64 == ~0ull) {
-        // two passes: tile counts, scan, write
-        uint32_t* tcnt = ctx.arena.get<uint32_t>("tile_cnt", (size_t)htiles + 1);
-        uint64_t* toff = ctx.arena.get<uint64_t>("tile_off", (size_t)htiles + 1);
-        hipLaunchKernelGGL((halo_tile_kernel<T, D>), dim3(htiles), dim3(kBlock), 0, s, X, n, parts, P,
-                           tcnt, ctrs, sort_hist);
-        R64 = tile_offsets(ctx, tcnt, htiles, toff, s, true);
-        if (R64 >= 0xFFFFFFFEull) throw Error(-5, "more than 2^32-2 halo records on one device");
-        keys = ctx.arena.get<K>("keys", R64);
-        vals = ctx.arena.get<uint32_t>("vals", R64);
-        if (P <= 64)
-            hipLaunchKernelGGL((halo_write_kernel<T, D, K, true>), dim3(htiles), dim3(kBlock), 0, s,
-                               X, n, parts, P, a.owner, tree, toff, R64, keys, vals);
-        else
-            hipLaunchKernelGGL((halo_write_kernel<T, D, K, false>), dim3(htiles), dim3(kBlock), 0,
-                               s, X, n, parts, P, a.owner, tree, toff, R64, keys, vals);
-        PD_HIP(hipGetLastError());
-        check_bounds(s, "halo_write_kernel");
-    }
+    // two passes: tile counts, scan, write
+    uint32_t* tcnt = ctx.arena.get<uint32_t>("tile_cnt", (size_t)htiles + 1);
+    uint64_t* toff = ctx.arena.get<uint64_t>("tile_off", (size_t)htiles + 1);
+    hipLaunchKernelGGL((halo_tile_kernel<T, D>), dim3(htiles), dim3(kBlock), 0, s, X, n, parts, P,
+                       tcnt, ctrs, sort_hist);
+    const uint64_t R64 = tile_offsets(ctx, tcnt, htiles, toff, s, true);
+    if (R64 >= 0xFFFFFFFEull) throw Error(-5, "more than 2^32-2 halo records on one device");
+    K* keys = ctx.arena.get<K>("keys", R64);
+    uint32_t* vals = ctx.arena.get<uint32_t>("vals", R64);
+    if (P <= 64)
+        hipLaunchKernelGGL((halo_write_kernel<T, D, K, true>), dim3(htiles), dim3(kBlock), 0, s, X,
+                           n, parts, P, a.owner, tree, toff, R64, keys, vals);
+    else
+        hipLaunchKernelGGL((halo_write_kernel<T, D, K, false>), dim3(htiles), dim3(kBlock), 0, s, X,
+                           n, parts, P, a.owner, tree, toff, R64, keys, vals);
+    PD_HIP(hipGetLastError());
+    check_bounds(s, "halo_write_kernel");
     const uint32_t R = (uint32_t)R64;
     ctx.t.records = R;
-    ctx.h1_ratio = n ? (double)R / (double)n : 1.0;
-    keys2 = ctx.arena.get<K>("keys2", R);
-    vals2 = ctx.arena.get<uint32_t>("vals2", R);
+    K* keys2 = ctx.arena.get<K>("keys2", R);
+    uint32_t* vals2 = ctx.arena.get<uint32_t>("vals2", R);
     tm.mark();   // 1
 
     // ---- shuffle by neighbourhood == sort by (neighbourhood, cell) key:
