@@ -558,6 +558,21 @@ int32_t pd_index_build(pd_ctx* ctx, const void* X, int32_t dtype, int64_t n, int
  * the stream. */
 int32_t pd_index_query(pd_index* index, const void* Q, int32_t dtype, int64_t m,
                        int32_t* out, void* stream);
+/* k-distance (the sorted k-distance plot that picks eps; OPTICS / HDBSCAN core
+ * distance): build the index over ALL rows (core = ones, labels = zeros) with
+ * eps = the cap r_max.  The accumulator is the predicate's own: fp64, per-axis
+ * difference squared (cityblock: absolute value), summed in axis order, every
+ * product and sum rounded separately — the squared distance for euclidean — so
+ * for any eps <= r_max and k = min_samples a train's core flag of row i equals
+ * out[i] <= eps*eps (cityblock: <= eps) exactly.  Duplicates and ties each
+ * count, and a query that is a row counts itself at 0. */
+#define PD_KDIST_MAX_K 64
+/* out[m] (fp64, input order): the k-th smallest accumulator among the index's rows within the
+ * index's eps of each query (+inf: fewer than k).  Q as for pd_index_query.  1 <= k <=
+ * PD_KDIST_MAX_K (64): PD_EINVAL for k < 1, PD_EUNSUPPORTED above.  NaN/inf query: PD_EINVAL.
+ * Synchronises the stream. */
+int32_t pd_index_kdist(pd_index* index, const void* Q, int32_t dtype, int64_t m, int32_t k,
+                       double* out, void* stream);
 int32_t pd_index_destroy(pd_index* index);
 
 /* ---- RCCL collectives of the sharded train (one rank per device).  They

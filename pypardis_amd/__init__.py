@@ -22,5 +22,6 @@ from .partition import (
 from .dbscan import (
     dbscan_partition,
     map_cluster_id,
-    DBSCAN
+    DBSCAN,
+    k_distances
 )

@@ -62,7 +62,7 @@ EXPORTS = ["pd_abi_version", "pd_last_error", "pd_ctx_create", "pd_ctx_destroy",
            "pd_pack2", "pd_results", "pd_results_scatter", "pd_comm_exchange", "pd_comm_abort",
            "pd_comm_self_check", "pd_comm_size", "pd_index_build", "pd_index_query",
            "pd_index_destroy", "pd_cluster_weighted", "pd_train_weighted",
-           "pd_train_tree_weighted"]
+           "pd_train_tree_weighted", "pd_index_kdist"]
 
 
 class PardisError(RuntimeError):
@@ -155,6 +155,7 @@ def load():
             "pd_comm_size": ([P, P, P], I32),
             "pd_index_build": ([P, P, I32, I64, I32, P, P, D, I32, ctypes.POINTER(P), P, P], I32),
             "pd_index_query": ([P, P, I32, I64, P, P], I32),
+            "pd_index_kdist": ([P, P, I32, I64, I32, P, P], I32),
             "pd_index_destroy": ([P], I32),
             "pd_cluster_weighted": ([P, P, I32, I64, I32, D, I32, I32, P, P, P, P, P], I32),
             "pd_train_weighted": ([P, P, I32, I64, I32, D, I32, I32, I32, P, P, P, P, P, P, P, P],
@@ -555,6 +556,7 @@ def train_tree(X, eps, min_samples, metric, ebox, tree, data_box=None, want_coun
 
 # ------------------------------------------------------------ assignment index
 PD_EINVAL = -1
+KDIST_MAX_K = 64   # PD_KDIST_MAX_K
 
 
 class Index:
@@ -606,6 +608,32 @@ class Index:
         _check(load().pd_index_query(self.ptr, Q.data_ptr() if m else None, dt, m,
                                      out.data_ptr() if m else None, _stream(Q.device)))
         return out
+
+    def kdist(self, Q, k):
+        """float64 device tensor in the order of ``Q``: the k-th smallest
+        accumulator (squared distance; cityblock: the distance) among the
+        index's rows within its ``eps`` of each query, ``inf`` where fewer
+        than k are (pd_index_kdist).  1 <= k <= KDIST_MAX_K."""
+        if self.ptr is None:
+            raise ValueError("the index was closed")
+        dt = _check_points(Q)
+        if Q.shape[1] != self.d:
+            raise ValueError(f"queries have {Q.shape[1]} columns, the index was built on {self.d}")
+        if Q.device != self.device:
+            raise ValueError(f"queries are on {Q.device}, the index on {self.device}")
+        m = Q.shape[0]
+        out = torch.empty(m, dtype=torch.float64, device=Q.device)
+        _check(load().pd_index_kdist(self.ptr, Q.data_ptr() if m else None, dt, m, int(k),
+                                     out.data_ptr() if m else None, _stream(Q.device)))
+        return out
+
+    @classmethod
+    def over_all(cls, X, r_max, metric=PD_EUCLIDEAN, ctx=None):
+        """The index over every row of ``X`` with ``eps = r_max`` (a mask of
+        ones, labels of zero): what ``kdist`` is asked of."""
+        n = X.shape[0]
+        return cls(X, torch.ones(n, dtype=torch.uint8, device=X.device),
+                   torch.zeros(n, dtype=torch.int32, device=X.device), r_max, metric, ctx)
 
     def close(self):
         ptr, self.ptr = self.ptr, None

@@ -883,6 +883,16 @@ int32_t pd_index_query(pd_index* index, const void* Q, int32_t dtype, int64_t m,
     });
 }
 
+int32_t pd_index_kdist(pd_index* index, const void* Q, int32_t dtype, int64_t m, int32_t k,
+                       double* out, void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        if (m < 0 || (m && (!Q || !out))) throw Error(PD_EINVAL, "bad query arrays");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_kdist(index->ix, Q, dtype, m, k, out, (hipStream_t)stream);
+    });
+}
+
 int32_t pd_index_destroy(pd_index* index) {
     if (!index) return PD_OK;
     int32_t rc = guard(nullptr, [&] { index_destroy(index->ix); });

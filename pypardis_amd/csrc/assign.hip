@@ -34,6 +34,11 @@
 //
 // d > 4 — the compacted core rows, swept as LDS tiles by every query
 // (exact fp64, axis order; no MFMA screen: DESIGN.md §10).
+//
+// The same index built over ALL rows (mask of ones, eps = the cap r_max) also
+// answers k-distance queries (pd_index_kdist): the k-th smallest
+// accumulator within the cap, by the same row walk / tiles with a k-best list
+// per lane in place of the minimum label.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -478,6 +483,253 @@ __global__ __launch_bounds__(kBlock) void dense_query_kernel(
     if (gi < m) out[gi] = best == INT32_MAX ? -1 : best;
 }
 
+// ---------------------------------------------------------------- k-distance
+// kdist(q) = the k-th smallest accumulator (pred.hpp: squared distance, or the
+// cityblock sum) among the rows with acc <= thr, +inf when fewer than k qualify
+// (DESIGN.md §12).  No label prunes a cell here: every candidate of the 3^(D-1)
+// rows gets the exact fp64 accumulator, and what prunes is the moving bound
+// tau = min(thr, k-th best so far), which only the list itself lowers.
+
+// Device-side bounds checks of the k-distance kernels, engine.hip's scheme
+// (-DPD_CHECK_BOUNDS=1 builds): a checked access that would leave its buffer
+// is skipped and the first one recorded; the host reads the record after the
+// kernel and throws.  Off (the default) PD_OK is `true` and costs nothing.
+#ifndef PD_CHECK_BOUNDS
+#define PD_CHECK_BOUNDS 0
+#endif
+#if PD_CHECK_BOUNDS
+__device__ unsigned long long g_ix_oob[2];   // [0] violations, [1] the first
+__device__ __forceinline__ bool pd_ix_ok(bool c, unsigned site, uint64_t idx) {
+    if (!c && atomicAdd(&g_ix_oob[0], 1ull) == 0ull)
+        g_ix_oob[1] = ((unsigned long long)site << 48) | (idx & 0xFFFFFFFFFFFFull);
+    return c;
+}
+#define PD_OK(cond, site, idx) pd_ix_ok((cond), (site), (uint64_t)(idx))
+#else
+#define PD_OK(cond, site, idx) true
+#endif
+
+constexpr int kKdistMaxK = 64;
+
+// The k best accumulators of one lane, in registers: KT slots kept ascending
+// by a branch-free insert (slot s takes min(old s, max(old s-1, acc)): 2 KT
+// selects, every index a compile-time constant, so the list never leaves the
+// VGPRs).  A k below KT starts with KT - k slots at -inf, which no insert
+// moves, so the k-th best is always the last slot.
+template <int KT>
+struct RegList {
+    double b[KT];
+    double thr;
+    __device__ __forceinline__ void init(int k, double thr_) {
+        thr = thr_;
+#pragma unroll
+        for (int s = 0; s < KT; ++s) b[s] = s < KT - k ? -INFINITY : INFINITY;
+    }
+    __device__ __forceinline__ void offer(double acc) {
+        // tau = min(thr, k-th best): a tie with a full list's last slot changes nothing
+        if (!(acc <= thr && acc < b[KT - 1])) return;
+#pragma unroll
+        for (int s = KT - 1; s >= 1; --s) {
+            const double hi = b[s - 1] > acc ? b[s - 1] : acc;
+            b[s] = b[s] < hi ? b[s] : hi;
+        }
+        b[0] = b[0] < acc ? b[0] : acc;
+    }
+    __device__ __forceinline__ double result() const { return b[KT - 1]; }
+};
+
+// The same list in LDS for the larger k: best[slot][lane] (slot-major: the
+// lanes of a wave hit distinct banks whatever slots they are at), unordered,
+// with the largest entry's value and slot in registers.  Filling appends; a
+// full list replaces its largest entry and rescans the k slots for the next
+// one — k reads per accepted candidate, none per rejected one.
+struct LdsList {
+    double* my;      // this lane's slot 0
+    int stride;      // lanes per block
+    int k, cnt, imax;
+    double thr, top; // top: largest entry so far
+    __device__ __forceinline__ void init(double* base, int lane, int lanes, int k_, double thr_) {
+        my = base + lane;
+        stride = lanes;
+        k = k_;
+        cnt = 0;
+        imax = 0;
+        thr = thr_;
+        top = -INFINITY;
+    }
+    __device__ __forceinline__ double tau() const { return cnt < k ? thr : top; }
+    __device__ __forceinline__ void offer(double acc) {
+        if (cnt < k) {
+            if (!(acc <= thr)) return;
+            my[(size_t)cnt * stride] = acc;
+            if (acc >= top) {
+                top = acc;
+                imax = cnt;
+            }
+            ++cnt;
+        } else if (acc < top) {
+            my[(size_t)imax * stride] = acc;
+            top = -INFINITY;
+            for (int s = 0; s < k; ++s) {
+                const double v = my[(size_t)s * stride];
+                if (v > top) {
+                    top = v;
+                    imax = s;
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ double result() const { return cnt < k ? (double)INFINITY : top; }
+};
+
+// One lane per query, query_kernel's row walk (own row first, each row one key
+// run of <= 3 occupied cells, `order` for the sorted sweep, the same treatment
+// of queries outside the grid).  KT > 0: the list in registers (k <= KT);
+// KT == 0: in dynamic LDS, k * blockDim.x doubles.
+template <typename T, int D, int M, typename K, int KT>
+__global__ __launch_bounds__(kBlock) void kdist_kernel(
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxGrid g,
+    const T* __restrict__ Xs, uint64_t nrec, const K* __restrict__ ckey,
+    const uint32_t* __restrict__ cstart, const uint32_t* __restrict__ tab, uint64_t ntab,
+    uint32_t ncells, int shift, double thr, int k, double* __restrict__ out,
+    unsigned long long* __restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t qi = order ? (uint64_t)order[i] : i;
+    if (!PD_OK(qi < m, 40, qi)) return;
+    double a[D];
+    bool fin = true;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        a[j] = (double)Q[qi * D + j];
+        fin = fin && isfinite(a[j]);
+    }
+    if (!fin) {
+        atomicAdd(bad, 1ull);
+        out[qi] = INFINITY;
+        return;
+    }
+    int64_t c[D];
+    if (!cell_of<D>(a, g, c)) {   // more than a cell outside the rows' box
+        out[qi] = INFINITY;
+        return;
+    }
+    typename std::conditional<(KT > 0), RegList<(KT > 0 ? KT : 1)>, LdsList>::type list;
+    if constexpr (KT > 0)
+        list.init(k, thr);
+    else
+        list.init(reinterpret_cast<double*>(smem), (int)threadIdx.x, (int)blockDim.x, k, thr);
+    const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
+    const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
+    for (int rq = 0; rq < Rows<D>::v; ++rq) {
+        // the query's own row first: its rows fill the list with small values
+        const int r = (rq + Rows<D>::v / 2) % Rows<D>::v;
+        uint64_t base = 0;
+        bool ok = true;
+        int rr = r;
+#pragma unroll
+        for (int ax = D - 1; ax >= 1; --ax) {
+            int pw = 1;
+            for (int t = 1; t < ax; ++t) pw *= 3;
+            const int64_t y = c[ax] + (int64_t)(rr / pw) - 1;
+            rr %= pw;
+            ok = ok && y >= 0 && y < g.nc[ax];
+            base += (uint64_t)(ok ? y : 0) * g.stride[ax];
+        }
+        if (!ok) continue;
+        const uint64_t klo = base + (uint64_t)x0, khi = base + (uint64_t)x1;
+        const uint64_t b = klo >> shift;
+        if (!PD_OK(b + 1 < ntab, 41, b)) continue;
+        const uint32_t e0 = cell_lower_bound<K>(ckey, tab[b], tab[b + 1], klo);
+        uint32_t e1 = e0;
+        for (; e1 < ncells && (uint64_t)ckey[e1] <= khi; ++e1) {}   // <= 3 cells
+        if (e1 == e0) continue;
+        // occupied cells adjacent in ckey hold adjacent records: the row is one
+        // record run.  Four candidates' loads and sums are issued together (the
+        // loads do not wait on the list), then offered in record order.
+        uint32_t j = cstart[e0];
+        const uint32_t j1 = cstart[e1];
+        if (!PD_OK(j <= j1 && j1 <= nrec, 42, j1)) continue;
+        for (; j + 4 <= j1; j += 4) {
+            double acc4[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                double bv[D];
+                load_rec<T, D>(Xs, j + u, bv);
+                double acc = 0.0;
+#pragma unroll
+                for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
+                acc4[u] = acc;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) list.offer(acc4[u]);
+        }
+        for (; j < j1; ++j) {
+            double bv[D];
+            load_rec<T, D>(Xs, j, bv);
+            double acc = 0.0;
+#pragma unroll
+            for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
+            list.offer(acc);
+        }
+    }
+    out[qi] = list.result();
+}
+
+// d > kMaxDim: dense_query_kernel's tiles (queries transposed in LDS, rows
+// streamed through a tile every lane reads as a broadcast) with each lane's
+// list in LDS next to them.  The axis loop stops at the first partial sum
+// above tau: the sum never decreases, so such a pair could not enter the list.
+template <typename T, int M>
+__global__ __launch_bounds__(kBlock) void dense_kdist_kernel(
+    const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc, uint64_t nc, int TC,
+    double thr, int k, double* __restrict__ out, unsigned long long* __restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
+    double* Bs = reinterpret_cast<double*>(smem);            // [k][QB]
+    T* Qs = reinterpret_cast<T*>(Bs + (size_t)k * QB);       // [d][QB]
+    T* Cs = Qs + (size_t)d * QB;                             // [TC][d]
+    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
+    unsigned nf = 0;
+    for (int e = tid; e < QB * d; e += QB) {
+        const int row = e / d, ax = e % d;
+        const uint64_t gi = q0 + (uint64_t)row;
+        const T v = gi < m ? Q[gi * (uint64_t)d + ax] : (T)0;
+        nf += isfinite((double)v) ? 0u : 1u;
+        Qs[(size_t)ax * QB + row] = v;
+    }
+    if (nf) atomicAdd(bad, (unsigned long long)nf);
+    LdsList list;
+    list.init(Bs, tid, QB, k, thr);
+    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
+        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
+        __syncthreads();
+        for (int e = tid; e < tc * d; e += QB)
+            if (PD_OK(t0 * (uint64_t)d + e < nc * (uint64_t)d, 43, t0 * (uint64_t)d + e))
+                Cs[e] = Xc[t0 * (uint64_t)d + e];
+        __syncthreads();
+        for (int c = 0; c < tc; ++c) {
+            const T* cr = Cs + (size_t)c * d;
+            const double tau = list.tau();
+            double acc = 0.0;
+            for (int ax = 0; ax < d; ++ax) {
+                acc = within_axis<M>(acc, (double)Qs[(size_t)ax * QB + tid], (double)cr[ax]);
+                if (acc > tau) break;
+            }
+            if (acc <= tau) list.offer(acc);
+        }
+    }
+    const uint64_t gi = q0 + (uint64_t)tid;
+    if (gi < m) out[gi] = list.result();
+}
+
+__global__ __launch_bounds__(kBlock) void fill_f64_kernel(double* __restrict__ out, uint64_t m,
+                                                          double v) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < m) out[i] = v;
+}
+
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 uint64_t read_u64(Ctx& w, const unsigned long long* dev, int count, unsigned long long* host_out,
@@ -710,6 +962,132 @@ void query_t(Index& ix, const T* Q, uint64_t m, int32_t* out, hipStream_t s) {
     if (nbad) throw Error(-1, "pd_index_query: a query has a NaN or infinite coordinate");
 }
 
+void check_bounds_ix(hipStream_t s, const char* kernel) {
+#if PD_CHECK_BOUNDS
+    sync(s);
+    unsigned long long h[2] = {0, 0};
+    PD_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ix_oob), sizeof(h), 0, hipMemcpyDeviceToHost));
+    if (h[0]) {
+        const unsigned long long z[2] = {0, 0};
+        PD_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_ix_oob), z, sizeof(z), 0, hipMemcpyHostToDevice));
+        throw Error(-3, std::string(kernel) + ": " + std::to_string(h[0]) +
+                            " out-of-bounds accesses, first at site " + std::to_string(h[1] >> 48) +
+                            " index " + std::to_string(h[1] & 0xFFFFFFFFFFFFull));
+    }
+#else
+    (void)s;
+    (void)kernel;
+#endif
+}
+
+// The list tier of a run-time k (DESIGN.md §12 has the resource report behind
+// it): registers up to 8, LDS above, with the block sized so that the list of
+// a block stays at 32 KiB — 256 lanes up to k = 16, 128 up to 32, 64 up to 64.
+template <typename T, int D, int M, typename K, int KT>
+void kdist_launch(Index& ix, const T* Q, uint64_t m, const uint32_t* order, int k, int lanes,
+                  double thr, double* out, unsigned long long* bad, hipStream_t s) {
+    const size_t lds = KT > 0 ? 0 : (size_t)k * lanes * sizeof(double);
+    hipLaunchKernelGGL((kdist_kernel<T, D, M, K, KT>), dim3((unsigned)((m + lanes - 1) / lanes)),
+                       dim3(lanes), lds, s, Q, m, order, ix.g, (const T*)ix.Xs, ix.nc,
+                       (const K*)ix.ckey, ix.cstart, ix.tab, ix.ntab, ix.ncells, ix.shift, thr, k,
+                       out, bad);
+    PD_HIP(hipGetLastError());
+    check_bounds_ix(s, "kdist_kernel");
+}
+
+template <typename T, int D, int M, typename K>
+void kdist_grid(Index& ix, const T* Q, uint64_t m, int k, double thr, double* out,
+                unsigned long long* bad, hipStream_t s) {
+    Ctx& w = ix.work;
+    const uint32_t* order = nullptr;
+    if (m >= sort_min()) {
+        K* keys = w.arena.get<K>("q_keys", m);
+        uint32_t* vals = w.arena.get<uint32_t>("q_vals", m);
+        hipLaunchKernelGGL((query_key_kernel<T, D, K>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m,
+                           ix.g, keys, vals);
+        PD_HIP(hipGetLastError());
+        sort_pairs_inplace(w, keys, (int)sizeof(K), vals, m, ix.key_bits, s);
+        order = vals;
+    }
+    if (k <= 4)
+        kdist_launch<T, D, M, K, 4>(ix, Q, m, order, k, kBlock, thr, out, bad, s);
+    else if (k <= 8)
+        kdist_launch<T, D, M, K, 8>(ix, Q, m, order, k, kBlock, thr, out, bad, s);
+    else
+        kdist_launch<T, D, M, K, 0>(ix, Q, m, order, k, k <= 16 ? 256 : k <= 32 ? 128 : 64, thr,
+                                    out, bad, s);
+}
+
+template <typename T, int D, int M>
+void kdist_grid_k(Index& ix, const T* Q, uint64_t m, int k, double thr, double* out,
+                  unsigned long long* bad, hipStream_t s) {
+    if (ix.key_bytes == 4)
+        kdist_grid<T, D, M, uint32_t>(ix, Q, m, k, thr, out, bad, s);
+    else
+        kdist_grid<T, D, M, uint64_t>(ix, Q, m, k, thr, out, bad, s);
+}
+
+template <typename T, int M>
+void kdist_dense(Index& ix, const T* Q, uint64_t m, int k, double thr, double* out,
+                 unsigned long long* bad, hipStream_t s) {
+    // LDS per lane: its query row and its k-slot list; per block also TC rows.
+    // The row limit is pd_index_query's (64 lanes of rows + one tile row in
+    // 60 KiB).  The block shrinks until its lanes' share is <= 48 KiB (never
+    // below 64 lanes); what then passes 60 KiB in all (long rows with a large
+    // k) asks for up to 144 KiB of the CU's 160 through the function attribute.
+    const size_t row = (size_t)ix.d * sizeof(T);
+    if ((size_t)64 * row + row + 4 > (60u << 10))
+        throw Error(-5, "pd_index_kdist: d too large for the tile kernel's LDS (d * itemsize <= 944)");
+    const size_t lane = row + (size_t)k * sizeof(double);
+    int QB = 256;
+    while (QB > 64 && (size_t)QB * lane > (48u << 10)) QB >>= 1;
+    const size_t budget = (size_t)QB * lane + row <= (60u << 10) ? (60u << 10) : (144u << 10);
+    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * lane) / row);
+    const size_t lds = (size_t)QB * lane + (size_t)TC * row;
+    if (lds > (64u << 10))
+        PD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_kdist_kernel<T, M>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((dense_kdist_kernel<T, M>), dim3((unsigned)((m + QB - 1) / QB)), dim3(QB),
+                       lds, s, Q, m, ix.d, (const T*)ix.Xs, ix.nc, TC, thr, k, out, bad);
+    PD_HIP(hipGetLastError());
+    check_bounds_ix(s, "dense_kdist_kernel");
+}
+
+template <typename T, int M>
+void kdist_m(Index& ix, const T* Q, uint64_t m, int k, double* out, unsigned long long* bad,
+             hipStream_t s) {
+    const double thr = M == 0 ? ix.eps * ix.eps : ix.eps;
+    switch (ix.d) {
+        case 1: kdist_grid_k<T, 1, M>(ix, Q, m, k, thr, out, bad, s); break;
+        case 2: kdist_grid_k<T, 2, M>(ix, Q, m, k, thr, out, bad, s); break;
+        case 3: kdist_grid_k<T, 3, M>(ix, Q, m, k, thr, out, bad, s); break;
+        case 4: kdist_grid_k<T, 4, M>(ix, Q, m, k, thr, out, bad, s); break;
+        default: kdist_dense<T, M>(ix, Q, m, k, thr, out, bad, s); break;
+    }
+}
+
+template <typename T>
+void kdist_t(Index& ix, const T* Q, uint64_t m, int k, double* out, hipStream_t s) {
+    Ctx& w = ix.work;
+    unsigned long long* bad = w.arena.get<unsigned long long>("q_bad", 1);
+    PD_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
+    if (ix.nc < (uint64_t)k) {   // fewer than k rows in all (also: an empty index)
+        hipLaunchKernelGGL((finite_kernel<T>), dim3(grid_for((int64_t)(m * ix.d), 1024)),
+                           dim3(kBlock), 0, s, Q, m * (uint64_t)ix.d, bad);
+        PD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(fill_f64_kernel, dim3(blocks(m)), dim3(kBlock), 0, s, out, m,
+                           (double)INFINITY);
+        PD_HIP(hipGetLastError());
+    } else if (ix.metric == 0) {
+        kdist_m<T, 0>(ix, Q, m, k, out, bad, s);
+    } else {
+        kdist_m<T, 1>(ix, Q, m, k, out, bad, s);
+    }
+    unsigned long long nbad = 0;
+    read_u64(w, bad, 1, &nbad, s);
+    if (nbad) throw Error(-1, "pd_index_kdist: a query has a NaN or infinite coordinate");
+}
+
 }  // namespace
 
 Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const uint8_t* core,
@@ -754,6 +1132,19 @@ void index_query(Index* ix, const void* Q, int dtype, int64_t m, int32_t* out, h
         query_t<float>(*ix, (const float*)Q, (uint64_t)m, out, s);
     else
         query_t<double>(*ix, (const double*)Q, (uint64_t)m, out, s);
+}
+
+void index_kdist(Index* ix, const void* Q, int dtype, int64_t m, int k, double* out,
+                 hipStream_t s) {
+    if (k < 1) throw Error(-1, "pd_index_kdist: k must be >= 1");
+    if (k > kKdistMaxK) throw Error(-5, "pd_index_kdist: k must be <= PD_KDIST_MAX_K (64)");
+    if (dtype != ix->dtype) throw Error(-1, "pd_index_kdist: the queries' dtype differs from the index's");
+    if (m >= 0xFFFFFFFFll) throw Error(-5, "pd_index_kdist: m must be < 2^32 - 1");
+    if (m == 0) return;
+    if (ix->dtype == 0)
+        kdist_t<float>(*ix, (const float*)Q, (uint64_t)m, k, out, s);
+    else
+        kdist_t<double>(*ix, (const double*)Q, (uint64_t)m, k, out, s);
 }
 
 void index_destroy(Index* ix) {

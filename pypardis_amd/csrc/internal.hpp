@@ -362,6 +362,8 @@ struct Index;
 Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const uint8_t* core,
                    const int32_t* labels, double eps, int metric, hipStream_t s);
 void index_query(Index* ix, const void* Q, int dtype, int64_t m, int32_t* out, hipStream_t s);
+void index_kdist(Index* ix, const void* Q, int dtype, int64_t m, int k, double* out,
+                 hipStream_t s);
 void index_destroy(Index* ix);
 int index_device(const Index* ix);
 int64_t index_cores(const Index* ix);

@@ -284,6 +284,70 @@ class _ShardedAssignments(object):
         return self.n_total
 
 
+def _check_kdist_args(k, r_max):
+    if int(k) != k or k < 1:
+        raise ValueError(f"k must be an integer >= 1, got {k!r}")
+    if k > _native.KDIST_MAX_K:
+        raise ValueError(f"k must be <= {_native.KDIST_MAX_K}, got {k!r}")
+    if not (r_max > 0) or not np.isfinite(r_max):
+        raise ValueError(f"r_max must be a finite value > 0, got {r_max!r}")
+    return int(k), float(r_max)
+
+
+def _k_distances(X, q, k, r_max, metric, squared):
+    """kdist of the rows of ``q`` against the rows of ``X`` (device tensors):
+    the index over all of X is built, asked once and closed."""
+    if q.shape[1] != X.shape[1]:
+        raise ValueError(f"k_distances: queries have {q.shape[1]} coordinates, the data "
+                         f"{X.shape[1]}")
+    if q.dtype != X.dtype:
+        q = q.to(X.dtype)
+    try:
+        index = _native.Index.over_all(X, r_max, metric)
+        try:
+            acc = index.kdist(q, k)
+        finally:
+            index.close()
+    except _native.PardisError as e:
+        if e.code == _native.PD_EINVAL and "NaN" in str(e):   # sklearn's ValueError
+            raise ValueError(str(e)) from None
+        raise
+    if squared or metric != _native.PD_EUCLIDEAN:
+        return acc
+    return torch.sqrt(acc)
+
+
+def k_distances(data, k, r_max, metric='euclidean', queries=None, squared=False, device=None):
+    """
+    :param data: the indexed points, in any form ``DBSCAN.train`` takes
+    :param k: which neighbour (1 <= k <= 64); a query that is itself a row of
+        ``data`` counts itself at distance 0, as ``min_samples`` does
+    :param r_max: cap of the search: only rows within ``r_max`` (the
+        predicate of a train at ``eps = r_max``) are looked at
+    :param metric: 'euclidean' or 'cityblock' (string or scipy callable)
+    :param queries: the query points (converted to the data's dtype, as in
+        ``predict``); None: the data itself
+    :param squared: euclidean only: return the squared distances — the native,
+        bit-reproducible accumulator — instead of their square roots
+    :return: device float64 tensor in query order: the distance to the k-th
+        nearest row of ``data``, ``inf`` where fewer than k rows lie within
+        ``r_max``
+
+    The sorted result is the k-distance plot that ``eps`` is read from (k =
+    ``min_samples``), the value itself the OPTICS / HDBSCAN core distance.
+    Exact: the accumulator is the train's own (fp64, axis order, every product
+    and sum rounded separately), so for any ``eps <= r_max`` a train with
+    ``min_samples = k`` marks point i core exactly when ``k_distances(...,
+    squared=True)[i] <= eps * eps`` (cityblock: ``<= eps``).  The cost grows
+    with the number of rows within ``r_max``.  Single device.
+    """
+    k, r_max = _check_kdist_args(k, r_max)
+    metric = _native.metric_code(metric)
+    X = as_points(data, device).X
+    q = X if queries is None else as_points(queries, X.device).X
+    return _k_distances(X, q, k, r_max, metric, squared)
+
+
 class DBSCAN(object):
     """
     :eps: nearest neighbor radius
@@ -304,7 +368,8 @@ class DBSCAN(object):
     ``core_sample_mask_`` (device uint8), ``core_sample_indices_`` (device
     int64, ascending), ``n_clusters_``; ``predict(points)`` assigns new
     points to the trained clusters, ``fit_predict(data)`` is ``train`` then
-    ``labels_``.
+    ``labels_``; ``k_distances()`` gives each point's distance to its k-th
+    nearest neighbour (the k-distance plot ``eps`` is read from).
 
     ``sample_weight`` (``train`` / ``fit_predict``; sklearn's ``fit``
     argument): one weight per point; a point is core when the weights of the
@@ -539,6 +604,43 @@ class DBSCAN(object):
             eps, metric = self._trained
             self._index = _native.Index(X, self.core_sample_mask_, self.labels_, eps, metric)
         return self._index.query(q)
+
+    def k_distances(self, data=None, k=None, r_max=None, squared=False):
+        """
+        :param data: query points, in any form ``train`` takes; None: the
+            training points against themselves
+        :param k: default ``min_samples``
+        :param r_max: default ``eps``
+        :param squared: as the module-level ``k_distances``
+        :return: as ``k_distances(points, k, r_max, metric)``: device float64,
+            the distance of each query to its k-th nearest point (itself
+            included), ``inf`` beyond ``r_max``
+
+        After a train the indexed set is the training points, and with the
+        defaults ``core_sample_mask_ == (k_distances() <= eps)`` up to the
+        rounding of the square root (exactly with ``squared=True`` against
+        ``eps * eps``).  Before any train ``data`` is required and is both the
+        indexed set and the queries.  After a ``group=`` train each rank holds
+        only its slice, so ``data=None`` raises; a given ``data`` is then
+        answered against itself.  The index is built and closed per call.
+        """
+        k, r_max = _check_kdist_args(self.min_samples if k is None else k,
+                                     self.eps if r_max is None else r_max)
+        metric = _native.metric_code(self.metric)
+        have = self._points is not None and not self._group_trained
+        if data is None:
+            if self._group_trained:
+                raise ValueError("k_distances() after a group= train needs data: each rank "
+                                 "holds only its slice of the points")
+            if not have:
+                raise ValueError("k_distances before train needs data")
+            X = q = self._points.X
+        elif have:
+            X = self._points.X
+            q = as_points(data, X.device).X
+        else:
+            X = q = as_points(data, self.device).X
+        return _k_distances(X, q, k, r_max, metric, squared)
 
     # ------------------------------------------------------------ multi-GPU
     def _sharded_checks(self, points):
