@@ -1633,17 +1633,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE))) v
 // make (4) cheap, never a source of labels.
 constexpr uint32_t kMixed = 0xFFFFFFFEu;
 
-// Root of x without path writes (L1 reads: a stale parent is still an
-// ancestor, so the walk ends at a root of some moment).
-__device__ __forceinline__ uint32_t root_l1(const uint32_t* par, uint32_t x) {
-    uint32_t p = ld_l1(par + x);
-    while (p != x) {
-        x = p;
-        p = ld_l1(par + x);
-    }
-    return x;
-}
-
 __device__ __forceinline__ uint32_t lds_find(const uint32_t* lp, uint32_t x) {
     uint32_t p = lp[x];
     while (p != x) {
@@ -1669,80 +1658,145 @@ __device__ __forceinline__ void lds_union(uint32_t* lp, uint32_t a, uint32_t b) 
 }
 
 // The window union (link step 2), with the flatten fused into the staging
-// and the edges reduced in LDS first.  A wave stages its 64 records
+// and the edges reduced in LDS first.  A wave stages K groups of 64 records
 // and the W after them with each one's current root (own records get it
-// written back: the flatten), each core lane tests the W records after it
-// and unions the core ones within eps of another tree in an LDS forest over
-// the window's slots; then each slot whose tree differs from its LDS
-// component's representative unites the two trees in the global forest —
-// one global union per pair of trees the window joins (the wave's edges
-// between the same two trees cost one), instead of a find per edge.
+// written back: the flatten), each core lane tests the W records after each
+// of its K records and unions the core ones within eps of another tree in an
+// LDS forest over the window's slots; then each slot whose tree differs from
+// its LDS component's representative unites the two trees in the global
+// forest — one global union per pair of trees the window joins (the wave's
+// edges between the same two trees cost one), instead of a find per edge.
+//
+// The kernel waits on its chain of dependent loads (row and parent, the root
+// walk, the union's finds and CAS), not on bandwidth or issue, so a lane
+// carries K records through the chain together: every load of a level is
+// issued before any is consumed, and the root walks advance in lock-step
+// rounds (one load per unresolved slot and round).  C2: 2.57 -> 1.97 ms at
+// K = 4; the wave then waits for the deepest of its 64 K + W walks (~20
+// rounds by PMC), so K = 8 at a third of the occupancy loses.
+// The LDS rows are private to their wave, so a wave-scope fence would do
+// between the phases; it measured the same as the block barrier (C2 link
+// 4.66 against 4.70 ms, each with a range of 0.06), so the plain barrier
+// stays.
+
+// Groups per wave: the largest power of two up to PD_WINDOW_GROUPS whose LDS
+// rows fit PD_WINDOW_LDS bytes per wave (5851 B: seven 4-wave blocks in a
+// CU's 160 KiB; float/3-D/W = 2 at K = 4 takes 5160 B).  Both are A/B
+// overrides (tools/build_variant.sh "-DPD_WINDOW_GROUPS=2").
+#ifndef PD_WINDOW_GROUPS
+#define PD_WINDOW_GROUPS 4
+#endif
+#ifndef PD_WINDOW_LDS
+#define PD_WINDOW_LDS 5851
+#endif
+static_assert(PD_WINDOW_LDS * (kBlock / 64) <= 65536, "a block's static LDS");
+
+constexpr int window_groups(int elem, int D, int W) {
+    int k = 1;
+    while (2 * k <= PD_WINDOW_GROUPS && (64 * 2 * k + W) * (elem * D + 8) <= PD_WINDOW_LDS) k *= 2;
+    return k;
+}
+
 template <typename T, int D, int M, int W, bool ST>
 __global__ __launch_bounds__(kBlock) void window_uf_kernel(const T* __restrict__ Xs, uint32_t R,
                                                            double eps, double eps2, float lo,
                                                            float hi, uint32_t* __restrict__ par,
                                                            unsigned long long* __restrict__ stats) {
-    constexpr int E = 64 + W;
-    static_assert(E <= 128, "two slots per lane");
+    constexpr int K = window_groups((int)sizeof(T), D, W);
+    constexpr int E = 64 * K + W;        // own slots [0, 64K), then the look-ahead
+    constexpr int S = (E + 63) / 64;     // slots per lane: e = lane + 64 i
+    static_assert(W >= 1 && W <= 64, "one look-ahead slot per lane");
     __shared__ T sx[kBlock / 64][E][D];
     __shared__ uint32_t sp[kBlock / 64][E];
     __shared__ uint32_t lp[kBlock / 64][E];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t b = xcd_block(blockIdx.x, gridDim.x) * kBlock + w * 64;
-    for (int e = lane; e < E; e += 64) {
+    const uint32_t b = xcd_block(blockIdx.x, gridDim.x) * (uint32_t)(kBlock * K) + w * (64 * K);
+    // staging, level 1: every row and parent of the lane
+    T v[S][D];
+    uint32_t p[S], p0[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        const int e = lane + 64 * i;
         const uint32_t j = b + e;
-        T v[D];
-        uint32_t p = kNone;
-        if (j < R) {
-            load_raw<T, D>(Xs, j, v);
-            p = ld_l1(par + j);
-            if (p != kNone && p != j) {
-                const uint32_t root = root_l1(par, p);
-                if (e < 64 && root != p) st_rlx(par + j, root);   // the flatten
-                p = root;
-            }
-        } else {
+        p0[i] = kNone;
 #pragma unroll
-            for (int k = 0; k < D; ++k) v[k] = T(0);
+        for (int k = 0; k < D; ++k) v[i][k] = T(0);
+        if (e < E && j >= b && j < R) {   // (j >= b: no wrap past 2^32)
+            load_raw<T, D>(Xs, j, v[i]);
+            p0[i] = ld_l1(par + j);
         }
+    }
+    // levels 2..: the root walks, one load per open slot and round (L1
+    // reads: a stale parent is still an ancestor, and indices only decrease,
+    // so every walk ends at a root of some moment)
+    uint32_t open = 0;
 #pragma unroll
-        for (int k = 0; k < D; ++k) sx[w][e][k] = v[k];
-        sp[w][e] = p;
-        lp[w][e] = (uint32_t)e;
+    for (int i = 0; i < S; ++i) {
+        p[i] = p0[i];
+        if (p0[i] != kNone && p0[i] != b + (uint32_t)(lane + 64 * i)) open |= 1u << i;
+    }
+    while (__any(open != 0)) {
+        uint32_t q[S];
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+            if (open >> i & 1u) q[i] = ld_l1(par + p[i]);
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+            if (open >> i & 1u) {
+                if (q[i] == p[i]) open &= ~(1u << i);
+                p[i] = q[i];
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        const int e = lane + 64 * i;
+        if (i < K && p[i] != p0[i]) st_rlx(par + b + e, p[i]);   // the flatten (own slots)
+        if (e < E) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) sx[w][e][k] = v[i][k];
+            sp[w][e] = p[i];
+            lp[w][e] = (uint32_t)e;
+        }
     }
     __syncthreads();
-    const uint32_t r = b + lane;
-    const uint32_t p0 = r < R ? sp[w][lane] : kNone;
     LinkStats st;
-    if (p0 != kNone) {
-        Pred<T, D, M> pr;
+    Pred<T, D, M> pr;
+    pr.eps = eps;
+    pr.eps2 = eps2;
+    pr.lo = lo;
+    pr.hi = hi;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        if (p[i] == kNone) continue;   // non-core, or past R
+        const int e = lane + 64 * i;
 #pragma unroll
         for (int k = 0; k < D; ++k) {
-            pr.ar[k] = sx[w][lane][k];
-            pr.a[k] = (double)pr.ar[k];
+            pr.ar[k] = v[i][k];
+            pr.a[k] = (double)v[i][k];
         }
-        pr.eps = eps;
-        pr.eps2 = eps2;
-        pr.lo = lo;
-        pr.hi = hi;
 #pragma unroll 4
         for (int k = 1; k <= W; ++k) {
-            const uint32_t pj = sp[w][lane + k];
-            if (pj == kNone || pj == p0 || r + k >= R) continue;   // non-core / same tree
+            const uint32_t pj = sp[w][e + k];
+            if (pj == kNone || pj == p[i]) continue;   // non-core (or past R) / same tree
             T bj[D];
 #pragma unroll
-            for (int q = 0; q < D; ++q) bj[q] = sx[w][lane + k][q];
+            for (int q = 0; q < D; ++q) bj[q] = sx[w][e + k][q];
             if constexpr (ST) ++st.cand;
             if (pr(bj)) {
                 if constexpr (ST) ++st.hit;
-                lds_union(lp[w], (uint32_t)lane, (uint32_t)(lane + k));
+                lds_union(lp[w], (uint32_t)e, (uint32_t)(e + k));
             }
         }
     }
     __syncthreads();
-    for (int e = lane; e < E; e += 64) {
-        const uint32_t pe = sp[w][e];
-        if (pe == kNone) continue;
+    // emission, each lane for its slots.  (Trying the CAS of the larger root
+    // onto the smaller before any confirm walk measured no better: C2 link
+    // 4.70 ms with it, 4.61 ms without, ranges 0.04 and 0.06.)
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        const int e = lane + 64 * i;
+        if (e >= E || p[i] == kNone) continue;
+        const uint32_t pe = p[i];
         const uint32_t lr = lds_find(lp[w], (uint32_t)e);
         const uint32_t pl = sp[w][lr];
         if (pl == pe) continue;
@@ -3014,12 +3068,15 @@ void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t
         }
         auto go = [&](auto Wc) {
             constexpr int Wv = decltype(Wc)::value;
+            // a block covers kBlock records per group of its waves
+            constexpr int Kw = window_groups((int)sizeof(T), D, Wv);
+            const unsigned wb = blocks(((uint64_t)R + Kw - 1) / Kw);
             if (sst)
-                hipLaunchKernelGGL((window_uf_kernel<T, D, M, Wv, true>), dim3(blocks(R)),
-                                   dim3(kBlock), 0, s, Xs, R, eps, eps2, slo, shi, par, sst);
+                hipLaunchKernelGGL((window_uf_kernel<T, D, M, Wv, true>), dim3(wb), dim3(kBlock), 0,
+                                   s, Xs, R, eps, eps2, slo, shi, par, sst);
             else
-                hipLaunchKernelGGL((window_uf_kernel<T, D, M, Wv, false>), dim3(blocks(R)),
-                                   dim3(kBlock), 0, s, Xs, R, eps, eps2, slo, shi, par, sst);
+                hipLaunchKernelGGL((window_uf_kernel<T, D, M, Wv, false>), dim3(wb), dim3(kBlock), 0,
+                                   s, Xs, R, eps, eps2, slo, shi, par, sst);
         };
         if (cw <= 2)
             go(std::integral_constant<int, 2>{});
