@@ -573,6 +573,41 @@ int32_t pd_index_query(pd_index* index, const void* Q, int32_t dtype, int64_t m,
  * Synchronises the stream. */
 int32_t pd_index_kdist(pd_index* index, const void* Q, int32_t dtype, int64_t m, int32_t k,
                        double* out, void* stream);
+/* Radius query: every row of the index within `radius` of each query, as CSR
+ * in query order — the eps-graph itself (sklearn's radius_neighbors).  A row x
+ * is a neighbour of q when acc(q, x) <= thr, with the accumulator above and
+ * thr = fl(radius * radius) computed in double (cityblock: radius): the
+ * predicate of a train at eps = radius.  Ties at exactly thr are in, duplicates
+ * each appear, a query that is a row contains itself at 0.  0 < radius <= the
+ * index's eps (PD_EINVAL otherwise, also for a non-finite radius: the cells
+ * cover only eps).  Q as for pd_index_query (dtype mismatch or a NaN/inf
+ * coordinate: PD_EINVAL; m < 2^32 - 1; d > 4: PD_EUNSUPPORTED beyond 944 bytes
+ * per row).  m == 0 and an index without rows are valid: every offset is 0.
+ *
+ * pd_index_radius_count: offsets (device, int64[m + 1]) = exclusive sums of
+ * the queries' neighbour counts, summed in 64 bits (the total passes 2^32 long
+ * before n does); offsets[m] and *total_host (nullable) = the number of pairs.
+ * Synchronises the stream once.
+ *
+ * pd_index_radius_fill repeats the walk and writes neighbour t of query q to
+ * element offsets[q] + t of ids (device, int32[capacity]) and, when acc is not
+ * null, of acc (device, fp64[capacity]: the accumulator, bit-reproducible).
+ * ids holds the index's LABEL of the hit row — the `labels` value given to
+ * pd_index_build: build with labels[i] = i to get row numbers; on a predict
+ * index they are the cluster labels of the cores within the radius.  The order
+ * inside a query's segment is unspecified, but fixed for a given index and
+ * call.  Nothing is kept between the two calls: the caller passes the same Q
+ * and radius and the offsets of the count.  The fill never stores outside
+ * [offsets[q], min(offsets[q + 1], capacity)), whatever offsets holds, and
+ * returns PD_EINVAL when a query's neighbour count differs from the length of
+ * its segment or a segment passes capacity (Q, radius or offsets changed since
+ * the count); ids and acc are then unspecified inside the segments and
+ * untouched outside.  Synchronises the stream. */
+int32_t pd_index_radius_count(pd_index* index, const void* Q, int32_t dtype, int64_t m,
+                              double radius, int64_t* offsets, int64_t* total_host, void* stream);
+int32_t pd_index_radius_fill(pd_index* index, const void* Q, int32_t dtype, int64_t m,
+                             double radius, const int64_t* offsets, int32_t* ids, double* acc,
+                             int64_t capacity, void* stream);
 int32_t pd_index_destroy(pd_index* index);
 
 /* ---- RCCL collectives of the sharded train (one rank per device).  They

@@ -23,5 +23,6 @@ from .dbscan import (
     dbscan_partition,
     map_cluster_id,
     DBSCAN,
-    k_distances
+    k_distances,
+    radius_neighbors
 )

@@ -62,7 +62,8 @@ EXPORTS = ["pd_abi_version", "pd_last_error", "pd_ctx_create", "pd_ctx_destroy",
            "pd_pack2", "pd_results", "pd_results_scatter", "pd_comm_exchange", "pd_comm_abort",
            "pd_comm_self_check", "pd_comm_size", "pd_index_build", "pd_index_query",
            "pd_index_destroy", "pd_cluster_weighted", "pd_train_weighted",
-           "pd_train_tree_weighted", "pd_index_kdist"]
+           "pd_train_tree_weighted", "pd_index_kdist", "pd_index_radius_count",
+           "pd_index_radius_fill"]
 
 
 class PardisError(RuntimeError):
@@ -156,6 +157,8 @@ def load():
             "pd_index_build": ([P, P, I32, I64, I32, P, P, D, I32, ctypes.POINTER(P), P, P], I32),
             "pd_index_query": ([P, P, I32, I64, P, P], I32),
             "pd_index_kdist": ([P, P, I32, I64, I32, P, P], I32),
+            "pd_index_radius_count": ([P, P, I32, I64, D, P, P, P], I32),
+            "pd_index_radius_fill": ([P, P, I32, I64, D, P, P, P, I64, P], I32),
             "pd_index_destroy": ([P], I32),
             "pd_cluster_weighted": ([P, P, I32, I64, I32, D, I32, I32, P, P, P, P, P], I32),
             "pd_train_weighted": ([P, P, I32, I64, I32, D, I32, I32, I32, P, P, P, P, P, P, P, P],
@@ -593,6 +596,7 @@ class Index:
         self.device = X.device
         self.dtype = X.dtype
         self.d = int(d)
+        self.eps = float(eps)
         self.n_core = int(nc[0])
 
     def query(self, Q):
@@ -626,6 +630,85 @@ class Index:
         _check(load().pd_index_kdist(self.ptr, Q.data_ptr() if m else None, dt, m, int(k),
                                      out.data_ptr() if m else None, _stream(Q.device)))
         return out
+
+    def _radius_args(self, Q, radius):
+        if self.ptr is None:
+            raise ValueError("the index was closed")
+        dt = _check_points(Q)
+        if Q.shape[1] != self.d:
+            raise ValueError(f"queries have {Q.shape[1]} columns, the index was built on {self.d}")
+        if Q.device != self.device:
+            raise ValueError(f"queries are on {Q.device}, the index on {self.device}")
+        return dt, float(self.eps if radius is None else radius)
+
+    def radius_count(self, Q, radius=None):
+        """-> (indptr, total): int64 device tensor of m + 1 offsets (the
+        exclusive sums of the queries' neighbour counts within ``radius``,
+        default the index's ``eps``) and their total as a Python int
+        (pd_index_radius_count)."""
+        dt, radius = self._radius_args(Q, radius)
+        m = Q.shape[0]
+        indptr = torch.empty(m + 1, dtype=torch.int64, device=Q.device)
+        total = np.zeros(1, np.int64)
+        _check(load().pd_index_radius_count(self.ptr, Q.data_ptr() if m else None, dt, m, radius,
+                                            indptr.data_ptr(), total.ctypes.data,
+                                            _stream(Q.device)))
+        return indptr, int(total[0])
+
+    def radius_fill(self, Q, radius, indptr, ids, acc=None, capacity=None):
+        """Write the neighbours of each query into its segment of ``ids``
+        (int32) and ``acc`` (float64, optional) as ``indptr`` lays them out
+        (pd_index_radius_fill).  ``capacity``: elements of ``ids`` / ``acc``
+        the fill may use, default all of ``ids``.  Raises PardisError
+        (PD_EINVAL) when the offsets do not match the query."""
+        dt, radius = self._radius_args(Q, radius)
+        m = Q.shape[0]
+        if indptr.dtype != torch.int64 or indptr.shape != (m + 1,) or not indptr.is_contiguous():
+            raise ValueError("indptr must be a contiguous int64 tensor of m + 1 offsets")
+        if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+            raise ValueError("ids must be a contiguous int32 vector")
+        cap = ids.shape[0] if capacity is None else int(capacity)
+        if cap > ids.shape[0]:
+            raise ValueError("capacity passes the end of ids")
+        if acc is not None:
+            if acc.dtype != torch.float64 or acc.dim() != 1 or not acc.is_contiguous():
+                raise ValueError("acc must be a contiguous float64 vector")
+            if cap > acc.shape[0]:
+                raise ValueError("capacity passes the end of acc")
+        if any(t.device != self.device for t in (indptr, ids) + (() if acc is None else (acc,))):
+            raise ValueError(f"indptr, ids and acc must be on {self.device}")
+        _check(load().pd_index_radius_fill(self.ptr, Q.data_ptr() if m else None, dt, m, radius,
+                                           indptr.data_ptr(), ids.data_ptr() if cap else None,
+                                           acc.data_ptr() if acc is not None and cap else None,
+                                           cap, _stream(Q.device)))
+
+    def radius(self, Q, radius=None, return_acc=True, count_only=False):
+        """-> (indptr, ids, acc): the rows within ``radius`` (default the
+        index's ``eps``; never above it) of each query, as CSR in the order of
+        ``Q``: ``ids[indptr[q]:indptr[q + 1]]`` are the index's labels of the
+        neighbours of query q — row numbers for ``over_rows`` — in an
+        unspecified but reproducible order, ``acc`` (float64, None unless
+        ``return_acc``) their accumulators.  ``ids`` and ``acc`` are allocated
+        after the count; ``count_only`` stops there and returns
+        (indptr, None, None)."""
+        indptr, total = self.radius_count(Q, radius)
+        if count_only:
+            return indptr, None, None
+        ids = torch.empty(total, dtype=torch.int32, device=Q.device)
+        acc = torch.empty(total, dtype=torch.float64, device=Q.device) if return_acc else None
+        self.radius_fill(Q, radius, indptr, ids, acc)
+        return indptr, ids, acc
+
+    @classmethod
+    def over_rows(cls, X, r_max, metric=PD_EUCLIDEAN, ctx=None):
+        """The index over every row of ``X`` with ``eps = r_max`` whose labels
+        are the row numbers (a mask of ones, labels 0 .. n-1): what ``radius``
+        is asked of."""
+        n = X.shape[0]
+        if n > 2**31 - 1:
+            raise ValueError(f"over_rows: {n} rows do not fit int32 row numbers")
+        return cls(X, torch.ones(n, dtype=torch.uint8, device=X.device),
+                   torch.arange(n, dtype=torch.int32, device=X.device), r_max, metric, ctx)
 
     @classmethod
     def over_all(cls, X, r_max, metric=PD_EUCLIDEAN, ctx=None):

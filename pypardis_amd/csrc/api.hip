@@ -893,6 +893,30 @@ int32_t pd_index_kdist(pd_index* index, const void* Q, int32_t dtype, int64_t m,
     });
 }
 
+int32_t pd_index_radius_count(pd_index* index, const void* Q, int32_t dtype, int64_t m,
+                              double radius, int64_t* offsets, int64_t* total_host, void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        if (m < 0 || (m && !Q) || !offsets) throw Error(PD_EINVAL, "bad query arrays");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_radius_count(index->ix, Q, dtype, m, radius, offsets, total_host,
+                           (hipStream_t)stream);
+    });
+}
+
+int32_t pd_index_radius_fill(pd_index* index, const void* Q, int32_t dtype, int64_t m,
+                             double radius, const int64_t* offsets, int32_t* ids, double* acc,
+                             int64_t capacity, void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        if (m < 0 || (m && (!Q || !offsets)) || (capacity > 0 && !ids))
+            throw Error(PD_EINVAL, "bad query arrays");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_radius_fill(index->ix, Q, dtype, m, radius, offsets, ids, acc, capacity,
+                          (hipStream_t)stream);
+    });
+}
+
 int32_t pd_index_destroy(pd_index* index) {
     if (!index) return PD_OK;
     int32_t rc = guard(nullptr, [&] { index_destroy(index->ix); });

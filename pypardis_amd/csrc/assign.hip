@@ -38,7 +38,10 @@
 // The same index built over ALL rows (mask of ones, eps = the cap r_max) also
 // answers k-distance queries (pd_index_kdist): the k-th smallest
 // accumulator within the cap, by the same row walk / tiles with a k-best list
-// per lane in place of the minimum label.
+// per lane in place of the minimum label — and radius queries
+// (pd_index_radius_count / _fill): every row within a radius
+// <= eps of each query, as CSR, by the same walk / tiles in a count pass, a
+// 64-bit scan of the counts and a fill pass that writes each hit's label.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -730,6 +733,208 @@ __global__ __launch_bounds__(kBlock) void fill_f64_kernel(double* __restrict__ o
     if (i < m) out[i] = v;
 }
 
+// ---------------------------------------------------------------- radius query
+// neighbours(q) = every row with acc(q, x) <= thr, thr = fl(radius * radius)
+// (cityblock: radius) for a radius <= the index's eps: the predicate of a train
+// at eps = radius.  Two passes over the same candidates with the
+// same exact fp64 sum (no fp32 screen: Pred's band belongs to the index's eps):
+// FILL == 0 counts each query's hits, the host scans the counts into 64-bit
+// offsets, and FILL == 1 (labels) / 2 (labels and accumulators) writes hit t of
+// query q to off[q] + t.
+//
+// One query's side of either pass.  The fill trusts nothing about `off`: a hit
+// is stored only inside [off[q], min(off[q + 1], cap)) — a segment that is not
+// 0 <= off[q] <= off[q + 1], or that starts beyond cap, takes no store at all —
+// and a query whose hit count differs from its segment's length (or whose
+// segment passes cap) is tallied, so a stale or foreign offsets array ends as
+// an error code, never as a stray store.
+template <int FILL>
+struct RadiusRow {
+    uint32_t n;             // hits so far
+    int64_t pos, end, lim;  // FILL: stores go to [pos, lim)
+    bool ok;
+    __device__ __forceinline__ void open(const int64_t* __restrict__ off, uint64_t qi, uint64_t m,
+                                         int64_t cap) {
+        n = 0;
+        if constexpr (FILL > 0) {
+            ok = PD_OK(qi + 1 <= m, 45, qi);
+            const int64_t p = ok ? off[qi] : 0;
+            end = ok ? off[qi + 1] : 0;
+            ok = ok && p >= 0 && p <= end && p <= cap;
+            pos = ok ? p : 0;
+            lim = ok ? (end < cap ? end : cap) : 0;
+        }
+    }
+    __device__ __forceinline__ void offer(double acc, double thr, const int32_t* __restrict__ lab,
+                                          uint32_t j, int32_t* __restrict__ ids,
+                                          double* __restrict__ accs) {
+        if (!(acc <= thr)) return;
+        if constexpr (FILL > 0) {
+            const int64_t w = pos + (int64_t)n;   // pos <= cap: no overflow
+            if (w < lim) {
+                ids[w] = lab[j];
+                if constexpr (FILL == 2) accs[w] = acc;
+            }
+        }
+        ++n;
+    }
+    __device__ __forceinline__ void close(uint32_t* __restrict__ cnt, uint64_t qi, int64_t cap,
+                                          unsigned long long* __restrict__ tally) {
+        if constexpr (FILL == 0) {
+            cnt[qi] = n;
+        } else {
+            if (!ok || end > cap || (int64_t)n != end - pos) atomicAdd(tally + 1, 1ull);
+        }
+    }
+};
+
+// d <= 4: kdist_kernel's walk without the list — one lane per query, its own
+// row first, each row one contiguous record run, four candidates' loads and
+// sums in flight, `order` for the cell-sorted sweep, nothing for a query more
+// than a cell outside the grid.  Hits keep the walk's order, which a given
+// index and call fix.  tally[0]: non-finite queries; tally[1]: see RadiusRow.
+template <typename T, int D, int M, typename K, int FILL>
+__global__ __launch_bounds__(kBlock) void radius_kernel(
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxGrid g,
+    const T* __restrict__ Xs, const int32_t* __restrict__ lab, uint64_t nrec,
+    const K* __restrict__ ckey, const uint32_t* __restrict__ cstart,
+    const uint32_t* __restrict__ tab, uint64_t ntab, uint32_t ncells, int shift, double thr,
+    uint32_t* __restrict__ cnt, const int64_t* __restrict__ off, int32_t* __restrict__ ids,
+    double* __restrict__ accs, int64_t cap, unsigned long long* __restrict__ tally) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t qi = order ? (uint64_t)order[i] : i;
+    if (!PD_OK(qi < m, 44, qi)) return;
+    RadiusRow<FILL> row;
+    row.open(off, qi, m, cap);
+    double a[D];
+    bool fin = true;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        a[j] = (double)Q[qi * D + j];
+        fin = fin && isfinite(a[j]);
+    }
+    if (!fin) atomicAdd(tally, 1ull);
+    int64_t c[D];
+    if (fin && cell_of<D>(a, g, c)) {
+        const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
+        const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
+        for (int rq = 0; rq < Rows<D>::v; ++rq) {
+            const int r = (rq + Rows<D>::v / 2) % Rows<D>::v;
+            uint64_t base = 0;
+            bool in = true;
+            int rr = r;
+#pragma unroll
+            for (int ax = D - 1; ax >= 1; --ax) {
+                int pw = 1;
+                for (int t = 1; t < ax; ++t) pw *= 3;
+                const int64_t y = c[ax] + (int64_t)(rr / pw) - 1;
+                rr %= pw;
+                in = in && y >= 0 && y < g.nc[ax];
+                base += (uint64_t)(in ? y : 0) * g.stride[ax];
+            }
+            if (!in) continue;
+            const uint64_t klo = base + (uint64_t)x0, khi = base + (uint64_t)x1;
+            const uint64_t b = klo >> shift;
+            if (!PD_OK(b + 1 < ntab, 46, b)) continue;
+            const uint32_t e0 = cell_lower_bound<K>(ckey, tab[b], tab[b + 1], klo);
+            uint32_t e1 = e0;
+            for (; e1 < ncells && (uint64_t)ckey[e1] <= khi; ++e1) {}   // <= 3 cells
+            if (e1 == e0) continue;
+            uint32_t j = cstart[e0];
+            const uint32_t j1 = cstart[e1];
+            if (!PD_OK(j <= j1 && j1 <= nrec, 47, j1)) continue;
+            for (; j + 4 <= j1; j += 4) {
+                double acc4[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    double bv[D];
+                    load_rec<T, D>(Xs, j + u, bv);
+                    double acc = 0.0;
+#pragma unroll
+                    for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
+                    acc4[u] = acc;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) row.offer(acc4[u], thr, lab, j + u, ids, accs);
+            }
+            for (; j < j1; ++j) {
+                double bv[D];
+                load_rec<T, D>(Xs, j, bv);
+                double acc = 0.0;
+#pragma unroll
+                for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
+                row.offer(acc, thr, lab, j, ids, accs);
+            }
+        }
+    }
+    row.close(cnt, qi, cap, tally);
+}
+
+// d > kMaxDim: dense_query_kernel's tiles (queries transposed in LDS, rows and
+// — for a fill — their labels streamed through a tile every lane reads as a
+// broadcast).  The axis loop stops at the first partial sum above thr; a pair
+// that is accepted ran it to the end, so its accumulator is the full sum.
+template <typename T, int M, int FILL>
+__global__ __launch_bounds__(kBlock) void dense_radius_kernel(
+    const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc,
+    const int32_t* __restrict__ lab, uint64_t nc, int TC, double thr, uint32_t* __restrict__ cnt,
+    const int64_t* __restrict__ off, int32_t* __restrict__ ids, double* __restrict__ accs,
+    int64_t cap, unsigned long long* __restrict__ tally) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
+    T* Qs = reinterpret_cast<T*>(smem);                                  // [d][QB]
+    T* Cs = Qs + (size_t)d * QB;                                         // [TC][d]
+    int32_t* Ls = reinterpret_cast<int32_t*>(Cs + (size_t)TC * d);       // [TC]
+    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
+    unsigned nf = 0;
+    for (int e = tid; e < QB * d; e += QB) {
+        const int qr = e / d, ax = e % d;
+        const uint64_t gi = q0 + (uint64_t)qr;
+        const T v = gi < m ? Q[gi * (uint64_t)d + ax] : (T)0;
+        nf += isfinite((double)v) ? 0u : 1u;
+        Qs[(size_t)ax * QB + qr] = v;
+    }
+    if (nf) atomicAdd(tally, (unsigned long long)nf);
+    const uint64_t gi = q0 + (uint64_t)tid;
+    const bool live = gi < m;   // the block's tail lanes sweep a zero row and emit nothing
+    RadiusRow<FILL> row;
+    row.open(off, live ? gi : 0, m, cap);
+    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
+        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
+        __syncthreads();
+        for (int e = tid; e < tc * d; e += QB)
+            if (PD_OK(t0 * (uint64_t)d + e < nc * (uint64_t)d, 48, t0 * (uint64_t)d + e))
+                Cs[e] = Xc[t0 * (uint64_t)d + e];
+        if constexpr (FILL > 0)
+            for (int e = tid; e < tc; e += QB)
+                if (PD_OK(t0 + e < nc, 49, t0 + e)) Ls[e] = lab[t0 + e];
+        __syncthreads();
+        if (!live) continue;
+        for (int c = 0; c < tc; ++c) {
+            const T* cr = Cs + (size_t)c * d;
+            double acc = 0.0;
+            for (int ax = 0; ax < d; ++ax) {
+                acc = within_axis<M>(acc, (double)Qs[(size_t)ax * QB + tid], (double)cr[ax]);
+                if (acc > thr) break;
+            }
+            row.offer(acc, thr, Ls, (uint32_t)c, ids, accs);
+        }
+    }
+    if (live) row.close(cnt, gi, cap, tally);
+}
+
+// The fill of an empty index: every segment must be empty.
+__global__ __launch_bounds__(kBlock) void radius_empty_kernel(const int64_t* __restrict__ off,
+                                                              uint64_t m, int64_t cap,
+                                                              unsigned long long* __restrict__ tally) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    RadiusRow<1> row;
+    row.open(off, i, m, cap);
+    row.close(nullptr, i, cap, tally);
+}
+
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 uint64_t read_u64(Ctx& w, const unsigned long long* dev, int count, unsigned long long* host_out,
@@ -882,20 +1087,25 @@ void build_t(Index& ix, const T* X, int64_t n, const uint8_t* core, const int32_
         build_grid_d<T, uint64_t>(ix, X, clist, labels, s);
 }
 
+// The cell-sorted sweep's order of m queries (null below sort_min(): input
+// order): lane i of a query kernel takes query order[i].
+template <typename T, int D, typename K>
+const uint32_t* query_order(Index& ix, const T* Q, uint64_t m, hipStream_t s) {
+    if (m < sort_min()) return nullptr;
+    Ctx& w = ix.work;
+    K* keys = w.arena.get<K>("q_keys", m);
+    uint32_t* vals = w.arena.get<uint32_t>("q_vals", m);
+    hipLaunchKernelGGL((query_key_kernel<T, D, K>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m, ix.g,
+                       keys, vals);
+    PD_HIP(hipGetLastError());
+    sort_pairs_inplace(w, keys, (int)sizeof(K), vals, m, ix.key_bits, s);
+    return vals;
+}
+
 template <typename T, int D, int M, typename K>
 void query_grid(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
                 hipStream_t s) {
-    Ctx& w = ix.work;
-    const uint32_t* order = nullptr;
-    if (m >= sort_min()) {
-        K* keys = w.arena.get<K>("q_keys", m);
-        uint32_t* vals = w.arena.get<uint32_t>("q_vals", m);
-        hipLaunchKernelGGL((query_key_kernel<T, D, K>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m,
-                           ix.g, keys, vals);
-        PD_HIP(hipGetLastError());
-        sort_pairs_inplace(w, keys, (int)sizeof(K), vals, m, ix.key_bits, s);
-        order = vals;
-    }
+    const uint32_t* order = query_order<T, D, K>(ix, Q, m, s);
     hipLaunchKernelGGL((query_kernel<T, D, M, K>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m, order,
                        ix.g, (const T*)ix.Xs, ix.lab, (const K*)ix.ckey, ix.cstart, ix.clab, ix.tab,
                        ix.ncells, ix.shift, ix.eps, ix.eps * ix.eps, ix.slo, ix.shi, out, bad);
@@ -998,17 +1208,7 @@ void kdist_launch(Index& ix, const T* Q, uint64_t m, const uint32_t* order, int 
 template <typename T, int D, int M, typename K>
 void kdist_grid(Index& ix, const T* Q, uint64_t m, int k, double thr, double* out,
                 unsigned long long* bad, hipStream_t s) {
-    Ctx& w = ix.work;
-    const uint32_t* order = nullptr;
-    if (m >= sort_min()) {
-        K* keys = w.arena.get<K>("q_keys", m);
-        uint32_t* vals = w.arena.get<uint32_t>("q_vals", m);
-        hipLaunchKernelGGL((query_key_kernel<T, D, K>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m,
-                           ix.g, keys, vals);
-        PD_HIP(hipGetLastError());
-        sort_pairs_inplace(w, keys, (int)sizeof(K), vals, m, ix.key_bits, s);
-        order = vals;
-    }
+    const uint32_t* order = query_order<T, D, K>(ix, Q, m, s);
     if (k <= 4)
         kdist_launch<T, D, M, K, 4>(ix, Q, m, order, k, kBlock, thr, out, bad, s);
     else if (k <= 8)
@@ -1088,6 +1288,107 @@ void kdist_t(Index& ix, const T* Q, uint64_t m, int k, double* out, hipStream_t 
     if (nbad) throw Error(-1, "pd_index_kdist: a query has a NaN or infinite coordinate");
 }
 
+// One pass of a radius query: the count (cnt) or a fill (off, ids, acc, cap).
+struct RadiusCall {
+    double thr;
+    uint32_t* cnt;
+    const int64_t* off;
+    int32_t* ids;
+    double* acc;
+    int64_t cap;
+    unsigned long long* tally;   // [0] non-finite queries, [1] segments that do not fit their hits
+};
+
+template <typename T, int D, int M, typename K, int FILL>
+void radius_grid(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
+    const uint32_t* order = query_order<T, D, K>(ix, Q, m, s);
+    hipLaunchKernelGGL((radius_kernel<T, D, M, K, FILL>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m,
+                       order, ix.g, (const T*)ix.Xs, ix.lab, ix.nc, (const K*)ix.ckey, ix.cstart,
+                       ix.tab, ix.ntab, ix.ncells, ix.shift, rc.thr, rc.cnt, rc.off, rc.ids, rc.acc,
+                       rc.cap, rc.tally);
+    PD_HIP(hipGetLastError());
+    check_bounds_ix(s, "radius_kernel");
+}
+
+template <typename T, int D, int M, int FILL>
+void radius_grid_k(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
+    if (ix.key_bytes == 4)
+        radius_grid<T, D, M, uint32_t, FILL>(ix, Q, m, rc, s);
+    else
+        radius_grid<T, D, M, uint64_t, FILL>(ix, Q, m, rc, s);
+}
+
+template <typename T, int M, int FILL>
+void radius_dense(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
+    // pd_index_query's LDS plan: QB query rows + TC rows and labels in 60 KiB
+    const size_t row = (size_t)ix.d * sizeof(T);
+    int QB = 256;
+    while (QB > 64 && (size_t)QB * row > (32u << 10)) QB >>= 1;
+    const size_t budget = 60u << 10;
+    if ((size_t)QB * row + row + 4 > budget)
+        throw Error(-5, "pd_index_radius: d too large for the tile kernel's LDS (d * itemsize <= 944)");
+    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * row) / (row + 4));
+    const size_t lds = (size_t)QB * row + (size_t)TC * (row + 4);
+    hipLaunchKernelGGL((dense_radius_kernel<T, M, FILL>), dim3((unsigned)((m + QB - 1) / QB)),
+                       dim3(QB), lds, s, Q, m, ix.d, (const T*)ix.Xs, ix.lab, ix.nc, TC, rc.thr,
+                       rc.cnt, rc.off, rc.ids, rc.acc, rc.cap, rc.tally);
+    PD_HIP(hipGetLastError());
+    check_bounds_ix(s, "dense_radius_kernel");
+}
+
+template <typename T, int M, int FILL>
+void radius_m(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
+    switch (ix.d) {
+        case 1: radius_grid_k<T, 1, M, FILL>(ix, Q, m, rc, s); break;
+        case 2: radius_grid_k<T, 2, M, FILL>(ix, Q, m, rc, s); break;
+        case 3: radius_grid_k<T, 3, M, FILL>(ix, Q, m, rc, s); break;
+        case 4: radius_grid_k<T, 4, M, FILL>(ix, Q, m, rc, s); break;
+        default: radius_dense<T, M, FILL>(ix, Q, m, rc, s); break;
+    }
+}
+
+template <typename T, int FILL>
+void radius_f(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
+    if (ix.metric == 0)
+        radius_m<T, 0, FILL>(ix, Q, m, rc, s);
+    else
+        radius_m<T, 1, FILL>(ix, Q, m, rc, s);
+}
+
+// Either pass over a non-empty index; an empty one only checks the queries
+// (and, for a fill, that every segment is empty).
+template <typename T>
+void radius_t(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
+    if (ix.nc == 0) {
+        hipLaunchKernelGGL((finite_kernel<T>), dim3(grid_for((int64_t)(m * ix.d), 1024)),
+                           dim3(kBlock), 0, s, Q, m * (uint64_t)ix.d, rc.tally);
+        PD_HIP(hipGetLastError());
+        if (rc.off) {
+            hipLaunchKernelGGL(radius_empty_kernel, dim3(blocks(m)), dim3(kBlock), 0, s, rc.off, m,
+                               rc.cap, rc.tally);
+            PD_HIP(hipGetLastError());
+        }
+    } else if (!rc.off) {
+        radius_f<T, 0>(ix, Q, m, rc, s);
+    } else if (!rc.acc) {
+        radius_f<T, 1>(ix, Q, m, rc, s);
+    } else {
+        radius_f<T, 2>(ix, Q, m, rc, s);
+    }
+}
+
+double radius_threshold(const Index& ix, int dtype, int64_t m, double radius, const char* who) {
+    const std::string w(who);
+    if (!(radius > 0) || !std::isfinite(radius))
+        throw Error(-1, w + ": radius must be a finite value > 0");
+    if (radius > ix.eps)
+        throw Error(-1, w + ": radius exceeds the eps the index was built with (its cells cover "
+                        "only eps)");
+    if (dtype != ix.dtype) throw Error(-1, w + ": the queries' dtype differs from the index's");
+    if (m >= 0xFFFFFFFFll) throw Error(-5, w + ": m must be < 2^32 - 1");
+    return ix.metric == 0 ? radius * radius : radius;
+}
+
 }  // namespace
 
 Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const uint8_t* core,
@@ -1145,6 +1446,71 @@ void index_kdist(Index* ix, const void* Q, int dtype, int64_t m, int k, double* 
         kdist_t<float>(*ix, (const float*)Q, (uint64_t)m, k, out, s);
     else
         kdist_t<double>(*ix, (const double*)Q, (uint64_t)m, k, out, s);
+}
+
+void index_radius_count(Index* ix, const void* Q, int dtype, int64_t m, double radius,
+                        int64_t* offsets, int64_t* total_host, hipStream_t s) {
+    RadiusCall rc{};
+    rc.thr = radius_threshold(*ix, dtype, m, radius, "pd_index_radius_count");
+    if (total_host) *total_host = 0;
+    if (m == 0 || ix->nc == 0)
+        PD_HIP(hipMemsetAsync(offsets, 0, sizeof(int64_t) * ((size_t)m + 1), s));
+    if (m == 0) return;
+    Ctx& w = ix->work;
+    const uint64_t um = (uint64_t)m;
+    rc.tally = w.arena.get<unsigned long long>("q_bad", 2);
+    PD_HIP(hipMemsetAsync(rc.tally, 0, 2 * sizeof(unsigned long long), s));
+    if (ix->nc) {
+        rc.cnt = w.arena.get<uint32_t>("r_cnt", um + 1);
+        PD_HIP(hipMemsetAsync(rc.cnt + um, 0, sizeof(uint32_t), s));
+    }
+    if (ix->dtype == 0)
+        radius_t<float>(*ix, (const float*)Q, um, rc, s);
+    else
+        radius_t<double>(*ix, (const double*)Q, um, rc, s);
+    if (ix->nc) {
+        // 32-bit counts, 64-bit sums: the total passes 2^32 long before n does
+        uint64_t* off = reinterpret_cast<uint64_t*>(offsets);
+        size_t tb = 0;
+        PD_HIP(rocprim::exclusive_scan(nullptr, tb, rc.cnt, off, (uint64_t)0, (size_t)um + 1,
+                                       rocprim::plus<uint64_t>(), s));
+        void* tmp = w.arena.get<char>("r_scan_tmp", tb);
+        PD_HIP(rocprim::exclusive_scan(tmp, tb, rc.cnt, off, (uint64_t)0, (size_t)um + 1,
+                                       rocprim::plus<uint64_t>(), s));
+    }
+    // the non-finite tally and the total in one round trip
+    unsigned long long* h = (unsigned long long*)pinned(w, 2 * sizeof(unsigned long long));
+    PD_HIP(hipMemcpyAsync(h, rc.tally, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    PD_HIP(hipMemcpyAsync(h + 1, offsets + um, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    sync(s);
+    if (h[0]) throw Error(-1, "pd_index_radius_count: a query has a NaN or infinite coordinate");
+    if (total_host) *total_host = (int64_t)h[1];
+}
+
+void index_radius_fill(Index* ix, const void* Q, int dtype, int64_t m, double radius,
+                       const int64_t* offsets, int32_t* ids, double* acc, int64_t capacity,
+                       hipStream_t s) {
+    RadiusCall rc{};
+    rc.thr = radius_threshold(*ix, dtype, m, radius, "pd_index_radius_fill");
+    if (capacity < 0) throw Error(-1, "pd_index_radius_fill: capacity < 0");
+    if (m == 0) return;
+    Ctx& w = ix->work;
+    rc.off = offsets;
+    rc.ids = ids;
+    rc.acc = acc;
+    rc.cap = capacity;
+    rc.tally = w.arena.get<unsigned long long>("q_bad", 2);
+    PD_HIP(hipMemsetAsync(rc.tally, 0, 2 * sizeof(unsigned long long), s));
+    if (ix->dtype == 0)
+        radius_t<float>(*ix, (const float*)Q, (uint64_t)m, rc, s);
+    else
+        radius_t<double>(*ix, (const double*)Q, (uint64_t)m, rc, s);
+    unsigned long long t[2] = {0, 0};
+    read_u64(w, rc.tally, 2, t, s);
+    if (t[0]) throw Error(-1, "pd_index_radius_fill: a query has a NaN or infinite coordinate");
+    if (t[1])
+        throw Error(-1, "pd_index_radius_fill: " + std::to_string(t[1]) + " queries' hits do not "
+                        "fit their segments: Q, radius or offsets changed since the count");
 }
 
 void index_destroy(Index* ix) {

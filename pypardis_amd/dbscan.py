@@ -19,6 +19,8 @@ merge is hash-order dependent), and are independent of
 """
 from __future__ import annotations
 
+import collections
+
 import numpy as np
 import torch
 from scipy.spatial.distance import euclidean
@@ -348,6 +350,101 @@ def k_distances(data, k, r_max, metric='euclidean', queries=None, squared=False,
     return _k_distances(X, q, k, r_max, metric, squared)
 
 
+RadiusNeighbors = collections.namedtuple("RadiusNeighbors", ["indptr", "indices", "distances"])
+
+
+def _check_radius_args(radius):
+    if not (radius > 0) or not np.isfinite(radius):
+        raise ValueError(f"radius must be a finite value > 0, got {radius!r}")
+    return float(radius)
+
+
+def _sort_rows(indptr, indices, acc):
+    """Each CSR row ordered by (acc, index): three stable sorts, last key
+    first.  Temporaries: the int64 row number of every entry and int64
+    permutations, about 40 bytes per entry at the peak."""
+    counts = indptr[1:] - indptr[:-1]
+    rows = torch.repeat_interleave(torch.arange(counts.shape[0], device=indptr.device), counts)
+    perm = torch.sort(indices, stable=True).indices
+    perm = perm[torch.sort(acc[perm], stable=True).indices]
+    perm = perm[torch.sort(rows[perm], stable=True).indices]
+    return indices[perm], acc[perm]
+
+
+def _radius_neighbors(X, q, radius, metric, return_distance, squared, sort_results, count_only):
+    """The rows of ``X`` within ``radius`` of the rows of ``q`` (device
+    tensors): the index over all of X is built, asked once and closed."""
+    if q.shape[1] != X.shape[1]:
+        raise ValueError(f"radius_neighbors: queries have {q.shape[1]} coordinates, the data "
+                         f"{X.shape[1]}")
+    if q.dtype != X.dtype:
+        q = q.to(X.dtype)
+    try:
+        index = _native.Index.over_rows(X, radius, metric)
+        try:
+            indptr, indices, acc = index.radius(q, radius, return_distance or sort_results,
+                                                count_only)
+        finally:
+            index.close()
+    except _native.PardisError as e:
+        if e.code == _native.PD_EINVAL and "NaN" in str(e):   # sklearn's ValueError
+            raise ValueError(str(e)) from None
+        raise
+    if count_only:
+        return indptr[1:] - indptr[:-1]
+    if sort_results:
+        indices, acc = _sort_rows(indptr, indices, acc)
+    if not return_distance:
+        acc = None
+    elif not squared and metric == _native.PD_EUCLIDEAN:
+        acc = torch.sqrt(acc)
+    return RadiusNeighbors(indptr, indices, acc)
+
+
+def radius_neighbors(data, radius, metric='euclidean', queries=None, return_distance=True,
+                     squared=False, sort_results=False, count_only=False, device=None):
+    """
+    :param data: the indexed points, in any form ``DBSCAN.train`` takes (fewer
+        than 2^31 of them)
+    :param radius: the neighbourhood's radius: row x is a neighbour of query q
+        under the predicate of a train at ``eps = radius`` (ties at exactly
+        ``radius`` are in)
+    :param metric: 'euclidean' or 'cityblock' (string or scipy callable)
+    :param queries: the query points (converted to the data's dtype, as in
+        ``predict``); None: the data itself, and every point is then its own
+        neighbour at distance 0
+    :param return_distance: also return each neighbour's distance
+    :param squared: euclidean only: return the squared distances — the native,
+        bit-reproducible accumulator — instead of their square roots
+    :param sort_results: order each query's neighbours by (distance, index)
+        with torch sorts afterwards; needs the distances and about 40 bytes of
+        temporaries per pair.  Otherwise the order inside a row is unspecified
+        (it is reproducible for a given data set and call)
+    :param count_only: return only the int64 device tensor of the neighbour
+        counts per query; nothing per pair is allocated or written
+    :return: ``RadiusNeighbors(indptr, indices, distances)`` of device tensors,
+        the eps-graph in CSR form in query order: the neighbours of query q are
+        ``indices[indptr[q]:indptr[q + 1]]`` (int32 row numbers of ``data``;
+        ``indptr`` int64), ``distances`` (float64) alongside, None when not
+        asked for.  ``scipy.sparse.csr_matrix((distances, indices, indptr))``
+        after ``.cpu()`` is what ``sklearn.cluster.DBSCAN(metric=
+        'precomputed')`` takes.
+
+    Exact: the accumulator and the test are the train's own (fp64, axis order,
+    every product and sum rounded separately, ``<= radius * radius``), so the
+    rows with at least ``min_samples`` neighbours are a train's core points at
+    ``eps = radius``, and DBSCAN's labels follow from the graph alone.  Time
+    and memory grow with the number of pairs (12 bytes each, 4 without the
+    distances).  Single device.
+    """
+    radius = _check_radius_args(radius)
+    metric = _native.metric_code(metric)
+    X = as_points(data, device).X
+    q = X if queries is None else as_points(queries, X.device).X
+    return _radius_neighbors(X, q, radius, metric, return_distance, squared, sort_results,
+                             count_only)
+
+
 class DBSCAN(object):
     """
     :eps: nearest neighbor radius
@@ -369,7 +466,8 @@ class DBSCAN(object):
     int64, ascending), ``n_clusters_``; ``predict(points)`` assigns new
     points to the trained clusters, ``fit_predict(data)`` is ``train`` then
     ``labels_``; ``k_distances()`` gives each point's distance to its k-th
-    nearest neighbour (the k-distance plot ``eps`` is read from).
+    nearest neighbour (the k-distance plot ``eps`` is read from),
+    ``radius_neighbors()`` the eps-graph itself in CSR form.
 
     ``sample_weight`` (``train`` / ``fit_predict``; sklearn's ``fit``
     argument): one weight per point; a point is core when the weights of the
@@ -641,6 +739,43 @@ class DBSCAN(object):
         else:
             X = q = as_points(data, self.device).X
         return _k_distances(X, q, k, r_max, metric, squared)
+
+    def radius_neighbors(self, data=None, radius=None, return_distance=True, squared=False,
+                         sort_results=False, count_only=False):
+        """
+        :param data: query points, in any form ``train`` takes; None: the
+            training points against themselves
+        :param radius: default ``eps``
+        :return: as the module-level ``radius_neighbors(points, radius,
+            metric, ...)``, whose other parameters these are
+
+        After a train the indexed set is the training points, and with the
+        defaults the result is the graph the train clustered: the rows with at
+        least ``min_samples`` neighbours are ``core_sample_mask_``, the
+        components of the core-core edges are the clusters, and a border point
+        carries the smallest label among its core neighbours.  Before any
+        train ``data`` is required and is both the indexed set and the
+        queries.  After a ``group=`` train each rank holds only its slice, so
+        ``data=None`` raises; a given ``data`` is then answered against
+        itself.  The index is built and closed per call.
+        """
+        radius = _check_radius_args(self.eps if radius is None else radius)
+        metric = _native.metric_code(self.metric)
+        have = self._points is not None and not self._group_trained
+        if data is None:
+            if self._group_trained:
+                raise ValueError("radius_neighbors() after a group= train needs data: each rank "
+                                 "holds only its slice of the points")
+            if not have:
+                raise ValueError("radius_neighbors before train needs data")
+            X = q = self._points.X
+        elif have:
+            X = self._points.X
+            q = as_points(data, X.device).X
+        else:
+            X = q = as_points(data, self.device).X
+        return _radius_neighbors(X, q, radius, metric, return_distance, squared, sort_results,
+                                 count_only)
 
     # ------------------------------------------------------------ multi-GPU
     def _sharded_checks(self, points):
