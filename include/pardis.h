@@ -573,6 +573,30 @@ int32_t pd_index_query(pd_index* index, const void* Q, int32_t dtype, int64_t m,
  * Synchronises the stream. */
 int32_t pd_index_kdist(pd_index* index, const void* Q, int32_t dtype, int64_t m, int32_t k,
                        double* out, void* stream);
+/* k nearest rows (sklearn's NearestNeighbors.kneighbors; the k-NN graph of
+ * HDBSCAN's mutual reachability, LOF, k-NN density): on the same index, eps =
+ * the cap r_max.  The candidates of a query q are the rows x with acc(q, x) <=
+ * thr, acc the accumulator above and thr = fl(r_max * r_max) (cityblock:
+ * r_max); ties at thr are in.  The result for q is the k smallest candidates
+ * under the total order (acc, label) ascending, written in that order, where
+ * label is the `labels` value given to pd_index_build (build with labels[i] =
+ * i to get row numbers): among equal accumulators the smaller label wins and
+ * comes first, duplicates each appear, a query that is a row finds itself at 0.
+ * Equal (acc, label) pairs (possible only where labels repeat: a predict
+ * index) each count and each appear.  A query with c < k candidates gets its c
+ * pairs and then k - c slots of (-1, +inf): a query more than a cell outside
+ * the rows' box, an index with fewer than k rows, an index without rows.  The
+ * result depends on the rows and labels alone, never on how the index lays
+ * them out, and acc[q * k + k - 1] equals pd_index_kdist(k)'s out[q] bit for
+ * bit, +inf included.
+ *
+ * ids (device, int32[m * k]) and acc (device, fp64[m * k], nullable): row-major
+ * (m, k), query order, written in full.  Q as for pd_index_query.  Errors are
+ * pd_index_kdist's: k < 1, a dtype mismatch, a NaN/inf query: PD_EINVAL; k >
+ * PD_KDIST_MAX_K, m >= 2^32 - 1, d > 4 rows above 944 bytes: PD_EUNSUPPORTED;
+ * the index stays usable.  m == 0 is valid.  Synchronises the stream. */
+int32_t pd_index_kneighbors(pd_index* index, const void* Q, int32_t dtype, int64_t m, int32_t k,
+                            int32_t* ids, double* acc, void* stream);
 /* Radius query: every row of the index within `radius` of each query, as CSR
  * in query order — the eps-graph itself (sklearn's radius_neighbors).  A row x
  * is a neighbour of q when acc(q, x) <= thr, with the accumulator above and

@@ -24,5 +24,6 @@ from .dbscan import (
     map_cluster_id,
     DBSCAN,
     k_distances,
-    radius_neighbors
+    radius_neighbors,
+    kneighbors
 )

@@ -63,7 +63,7 @@ EXPORTS = ["pd_abi_version", "pd_last_error", "pd_ctx_create", "pd_ctx_destroy",
            "pd_comm_self_check", "pd_comm_size", "pd_index_build", "pd_index_query",
            "pd_index_destroy", "pd_cluster_weighted", "pd_train_weighted",
            "pd_train_tree_weighted", "pd_index_kdist", "pd_index_radius_count",
-           "pd_index_radius_fill"]
+           "pd_index_radius_fill", "pd_index_kneighbors"]
 
 
 class PardisError(RuntimeError):
@@ -157,6 +157,7 @@ def load():
             "pd_index_build": ([P, P, I32, I64, I32, P, P, D, I32, ctypes.POINTER(P), P, P], I32),
             "pd_index_query": ([P, P, I32, I64, P, P], I32),
             "pd_index_kdist": ([P, P, I32, I64, I32, P, P], I32),
+            "pd_index_kneighbors": ([P, P, I32, I64, I32, P, P, P], I32),
             "pd_index_radius_count": ([P, P, I32, I64, D, P, P, P], I32),
             "pd_index_radius_fill": ([P, P, I32, I64, D, P, P, P, I64, P], I32),
             "pd_index_destroy": ([P], I32),
@@ -630,6 +631,30 @@ class Index:
         _check(load().pd_index_kdist(self.ptr, Q.data_ptr() if m else None, dt, m, int(k),
                                      out.data_ptr() if m else None, _stream(Q.device)))
         return out
+
+    def kneighbors(self, Q, k, return_acc=True):
+        """-> (ids, acc): (m, k) int32 / float64 device tensors in the order
+        of ``Q``: the index's labels (row numbers for ``over_rows``) and the
+        accumulators of the k nearest rows within its ``eps`` of each query,
+        each row ordered by (acc, label) ascending, ``-1`` / ``inf`` in the
+        slots past the rows that qualify (pd_index_kneighbors).  ``acc`` is
+        None unless ``return_acc``.  1 <= k <= KDIST_MAX_K."""
+        if self.ptr is None:
+            raise ValueError("the index was closed")
+        dt = _check_points(Q)
+        if Q.shape[1] != self.d:
+            raise ValueError(f"queries have {Q.shape[1]} columns, the index was built on {self.d}")
+        if Q.device != self.device:
+            raise ValueError(f"queries are on {Q.device}, the index on {self.device}")
+        m = Q.shape[0]
+        kk = int(k) if 1 <= int(k) <= KDIST_MAX_K else 1   # a bad k is the library's to report
+        ids = torch.empty((m, kk), dtype=torch.int32, device=Q.device)
+        acc = torch.empty((m, kk), dtype=torch.float64, device=Q.device) if return_acc else None
+        _check(load().pd_index_kneighbors(self.ptr, Q.data_ptr() if m else None, dt, m, int(k),
+                                          ids.data_ptr() if m else None,
+                                          acc.data_ptr() if return_acc and m else None,
+                                          _stream(Q.device)))
+        return ids, acc
 
     def _radius_args(self, Q, radius):
         if self.ptr is None:

@@ -893,6 +893,16 @@ int32_t pd_index_kdist(pd_index* index, const void* Q, int32_t dtype, int64_t m,
     });
 }
 
+int32_t pd_index_kneighbors(pd_index* index, const void* Q, int32_t dtype, int64_t m, int32_t k,
+                            int32_t* ids, double* acc, void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        if (m < 0 || (m && (!Q || !ids))) throw Error(PD_EINVAL, "bad query arrays");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_kneighbors(index->ix, Q, dtype, m, k, ids, acc, (hipStream_t)stream);
+    });
+}
+
 int32_t pd_index_radius_count(pd_index* index, const void* Q, int32_t dtype, int64_t m,
                               double radius, int64_t* offsets, int64_t* total_host, void* stream) {
     return guard(nullptr, [&] {

@@ -41,7 +41,9 @@
 // per lane in place of the minimum label — and radius queries
 // (pd_index_radius_count / _fill): every row within a radius
 // <= eps of each query, as CSR, by the same walk / tiles in a count pass, a
-// 64-bit scan of the counts and a fill pass that writes each hit's label.
+// 64-bit scan of the counts and a fill pass that writes each hit's label —
+// and k-nearest queries (pd_index_kneighbors): the k-distance
+// walk / tiles with a list of (accumulator, label) pairs, written out in order.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -733,6 +735,345 @@ __global__ __launch_bounds__(kBlock) void fill_f64_kernel(double* __restrict__ o
     if (i < m) out[i] = v;
 }
 
+// ---------------------------------------------------------------- k nearest
+// kneighbors(q) = the k smallest (acc, label) pairs, ascending, among the rows
+// with acc <= thr; (-1, +inf) in the slots past them.  The
+// k-distance walk / tiles with the label beside every accumulator.  The order
+// is total, so the list's bound admits a tie with its worst entry and the label
+// settles it: tau = min(thr, worst acc) is tested with <=, and only a candidate
+// that passes it has its label fetched.  What a query keeps therefore depends
+// on the (acc, label) pairs alone, never on the order the walk meets them in.
+
+__device__ __forceinline__ bool pair_lt(double a, int32_t la, double b, int32_t lb) {
+    return a < b || (a == b && la < lb);
+}
+
+// Slot t of query qi's row.  A slot nothing reached (or that holds an overflowed
+// accumulator, which no finite cap admits) is written as (-1, +inf).
+__device__ __forceinline__ void knn_store(int32_t* __restrict__ ids, double* __restrict__ accs,
+                                          uint64_t qi, uint64_t m, int k, int t, double acc,
+                                          int32_t l) {
+    const uint64_t w = qi * (uint64_t)k + (uint64_t)t;   // m * k passes 2^31 (C2: from k = 22)
+    if (!PD_OK(w < m * (uint64_t)k, 53, w)) return;
+    const bool none = !(acc < INFINITY);
+    ids[w] = none ? -1 : l;
+    if (accs) accs[w] = none ? (double)INFINITY : acc;
+}
+
+// RegList with the label beside each accumulator: KT pairs kept ascending under
+// (acc, label) by the same branch-free insert on pairs (slot s takes min(old s,
+// max(old s-1, candidate))).  The KT - k padding slots hold (-inf, INT32_MIN),
+// below every candidate, so no insert moves them; empty slots hold (+inf,
+// INT32_MAX).  An equal pair is inserted beside its twin.
+template <int KT>
+struct RegPairs {
+    double b[KT];
+    int32_t l[KT];
+    double thr;
+    __device__ __forceinline__ void init(int k, double thr_) {
+        thr = thr_;
+#pragma unroll
+        for (int s = 0; s < KT; ++s) {
+            b[s] = s < KT - k ? -INFINITY : INFINITY;
+            l[s] = s < KT - k ? INT32_MIN : INT32_MAX;
+        }
+    }
+    __device__ __forceinline__ double tau() const { return thr < b[KT - 1] ? thr : b[KT - 1]; }
+    // lab[j]: the candidate's label, read only once acc has passed tau
+    __device__ __forceinline__ void offer(double acc, const int32_t* __restrict__ lab, uint32_t j) {
+        if (!(acc <= thr && acc <= b[KT - 1])) return;
+        const int32_t la = lab[j];
+        if (!pair_lt(acc, la, b[KT - 1], l[KT - 1])) return;
+#pragma unroll
+        for (int s = KT - 1; s >= 1; --s) {
+            const bool lo = pair_lt(acc, la, b[s - 1], l[s - 1]);
+            const double hb = lo ? b[s - 1] : acc;
+            const int32_t hl = lo ? l[s - 1] : la;
+            const bool take = pair_lt(hb, hl, b[s], l[s]);
+            b[s] = take ? hb : b[s];
+            l[s] = take ? hl : l[s];
+        }
+        const bool take = pair_lt(acc, la, b[0], l[0]);
+        b[0] = take ? acc : b[0];
+        l[0] = take ? la : l[0];
+    }
+    __device__ __forceinline__ void write(int32_t* __restrict__ ids, double* __restrict__ accs,
+                                          uint64_t qi, uint64_t m, int k) const {
+#pragma unroll
+        for (int s = 0; s < KT; ++s)
+            if (s >= KT - k) knn_store(ids, accs, qi, m, k, s - (KT - k), b[s], l[s]);
+    }
+};
+
+// LdsList with the labels in a second slot-major array (12 bytes per slot):
+// unordered, the largest PAIR's value, label and slot in registers.  A full
+// list replaces its largest pair and rescans; the row is ordered at write-out
+// by a selection pass over the lane's own slots (order()).
+struct LdsPairs {
+    double* my;       // this lane's slot 0
+    int32_t* myl;
+    int stride;       // lanes per block
+    int k, cnt, imax;
+    double thr, top;  // (top, ltop): largest pair so far
+    int32_t ltop;
+    __device__ __forceinline__ void init(double* base, int32_t* lbase, int lane, int lanes, int k_,
+                                         double thr_) {
+        my = base + lane;
+        myl = lbase + lane;
+        stride = lanes;
+        k = k_;
+        cnt = 0;
+        imax = 0;
+        thr = thr_;
+        top = -INFINITY;
+        ltop = INT32_MIN;
+    }
+    __device__ __forceinline__ double tau() const { return cnt < k ? thr : top; }
+    __device__ __forceinline__ void offer(double acc, const int32_t* __restrict__ lab, uint32_t j) {
+        if (!(acc <= tau())) return;
+        const int32_t la = lab[j];
+        if (cnt < k) {
+            my[(size_t)cnt * stride] = acc;
+            myl[(size_t)cnt * stride] = la;
+            if (!pair_lt(acc, la, top, ltop)) {
+                top = acc;
+                ltop = la;
+                imax = cnt;
+            }
+            ++cnt;
+        } else if (pair_lt(acc, la, top, ltop)) {
+            my[(size_t)imax * stride] = acc;
+            myl[(size_t)imax * stride] = la;
+            top = -INFINITY;
+            ltop = INT32_MIN;
+            for (int s = 0; s < k; ++s) {
+                const double v = my[(size_t)s * stride];
+                const int32_t lv = myl[(size_t)s * stride];
+                if (!pair_lt(v, lv, top, ltop)) {
+                    top = v;
+                    ltop = lv;
+                    imax = s;
+                }
+            }
+        }
+    }
+    // The selection pass, in place: slots 0 .. cnt-1 ascending, (+inf, -1) behind
+    // them.  Each step takes the smallest remaining pair to slot t and moves what
+    // slot t held into its place, so equal pairs are each kept.
+    __device__ __forceinline__ void order() {
+        for (int t = 0; t < k; ++t) {
+            double bv = INFINITY;
+            int32_t bl = -1;
+            if (t < cnt) {
+                int bs = t;
+                bv = my[(size_t)t * stride];
+                bl = myl[(size_t)t * stride];
+                for (int s = t + 1; s < cnt; ++s) {
+                    const double v = my[(size_t)s * stride];
+                    const int32_t lv = myl[(size_t)s * stride];
+                    if (pair_lt(v, lv, bv, bl)) {
+                        bv = v;
+                        bl = lv;
+                        bs = s;
+                    }
+                }
+                if (bs != t) {
+                    my[(size_t)bs * stride] = my[(size_t)t * stride];
+                    myl[(size_t)bs * stride] = myl[(size_t)t * stride];
+                }
+            }
+            my[(size_t)t * stride] = bv;
+            myl[(size_t)t * stride] = bl;
+        }
+    }
+};
+
+// kdist_kernel's walk (one lane per query, its own row first, each row one
+// record run, four candidates' loads and sums in flight, `order` for the
+// cell-sorted sweep) over a pair list.  KT > 0: in registers (k <= KT), each
+// lane stores its own row.  KT == 0: in dynamic LDS — k * blockDim.x doubles,
+// as many int32, a query number per lane — where each lane orders its row and
+// the block then stores the rows side by side (C2, k = 10, ids + acc of all
+// points: 80.7 -> 75.4 ms against each lane storing its own).  A non-finite
+// query and one more than a cell outside the grid keep an empty list: k slots
+// of (-1, +inf).
+template <typename T, int D, int M, typename K, int KT>
+__global__ __launch_bounds__(kBlock) void knn_kernel(
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxGrid g,
+    const T* __restrict__ Xs, const int32_t* __restrict__ lab, uint64_t nrec,
+    const K* __restrict__ ckey, const uint32_t* __restrict__ cstart,
+    const uint32_t* __restrict__ tab, uint64_t ntab, uint32_t ncells, int shift, double thr, int k,
+    int32_t* __restrict__ ids, double* __restrict__ accs, unsigned long long* __restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr bool kLds = KT == 0;   // its rows leave through a barrier: no lane exits early
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!kLds && i >= m) return;
+    bool live = i < m;
+    const uint64_t qi = live ? (order ? (uint64_t)order[i] : i) : 0;
+    if (!PD_OK(qi < m, 50, qi)) {
+        if (!kLds) return;
+        live = false;
+    }
+    double a[D];
+    bool fin = live;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        a[j] = live ? (double)Q[qi * D + j] : 0.0;
+        fin = fin && isfinite(a[j]);
+    }
+    if (live && !fin) atomicAdd(bad, 1ull);
+    typename std::conditional<(KT > 0), RegPairs<(KT > 0 ? KT : 1)>, LdsPairs>::type list;
+    if constexpr (KT > 0) {
+        list.init(k, thr);
+    } else {
+        double* Bs = reinterpret_cast<double*>(smem);
+        list.init(Bs, reinterpret_cast<int32_t*>(Bs + (size_t)k * blockDim.x), (int)threadIdx.x,
+                  (int)blockDim.x, k, thr);
+    }
+    int64_t c[D];
+    if (fin && cell_of<D>(a, g, c)) {
+        const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
+        const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
+        for (int rq = 0; rq < Rows<D>::v; ++rq) {
+            // the query's own row first: its rows fill the list with small values
+            const int r = (rq + Rows<D>::v / 2) % Rows<D>::v;
+            uint64_t base = 0;
+            bool in = true;
+            int rr = r;
+#pragma unroll
+            for (int ax = D - 1; ax >= 1; --ax) {
+                int pw = 1;
+                for (int t = 1; t < ax; ++t) pw *= 3;
+                const int64_t y = c[ax] + (int64_t)(rr / pw) - 1;
+                rr %= pw;
+                in = in && y >= 0 && y < g.nc[ax];
+                base += (uint64_t)(in ? y : 0) * g.stride[ax];
+            }
+            if (!in) continue;
+            const uint64_t klo = base + (uint64_t)x0, khi = base + (uint64_t)x1;
+            const uint64_t b = klo >> shift;
+            if (!PD_OK(b + 1 < ntab, 51, b)) continue;
+            const uint32_t e0 = cell_lower_bound<K>(ckey, tab[b], tab[b + 1], klo);
+            uint32_t e1 = e0;
+            for (; e1 < ncells && (uint64_t)ckey[e1] <= khi; ++e1) {}   // <= 3 cells
+            if (e1 == e0) continue;
+            uint32_t j = cstart[e0];
+            const uint32_t j1 = cstart[e1];
+            if (!PD_OK(j <= j1 && j1 <= nrec, 52, j1)) continue;   // covers Xs and lab alike
+            for (; j + 4 <= j1; j += 4) {
+                double acc4[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    double bv[D];
+                    load_rec<T, D>(Xs, j + u, bv);
+                    double acc = 0.0;
+#pragma unroll
+                    for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
+                    acc4[u] = acc;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) list.offer(acc4[u], lab, j + u);
+            }
+            for (; j < j1; ++j) {
+                double bv[D];
+                load_rec<T, D>(Xs, j, bv);
+                double acc = 0.0;
+#pragma unroll
+                for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
+                list.offer(acc, lab, j);
+            }
+        }
+    }
+    if constexpr (kLds) {
+        // the block's rows, ordered in LDS, leave side by side: consecutive lanes
+        // store consecutive slots of one row, 64 / k rows per store instruction
+        const int lanes = (int)blockDim.x, tid = (int)threadIdx.x;
+        double* Bs = reinterpret_cast<double*>(smem);
+        int32_t* Li = reinterpret_cast<int32_t*>(Bs + (size_t)k * lanes);
+        uint32_t* Qi = reinterpret_cast<uint32_t*>(Li + (size_t)k * lanes);
+        list.order();
+        Qi[tid] = live ? (uint32_t)qi : 0xFFFFFFFFu;   // m < 2^32 - 1
+        __syncthreads();
+        for (int e = tid; e < lanes * k; e += lanes) {
+            const int rl = e / k, t = e - rl * k;
+            const uint32_t q = Qi[rl];
+            if (q != 0xFFFFFFFFu)
+                knn_store(ids, accs, (uint64_t)q, m, k, t, Bs[(size_t)t * lanes + rl],
+                          Li[(size_t)t * lanes + rl]);
+        }
+    } else {
+        list.write(ids, accs, qi, m, k);
+    }
+}
+
+// d > kMaxDim: dense_kdist_kernel's tiles with the rows' labels streamed beside
+// them (as dense_radius_kernel's fill) and each lane's pair list in LDS.  The
+// axis loop stops at the first partial sum above tau; a sum equal to tau runs
+// to the end and is offered, where its label decides.
+template <typename T, int M>
+__global__ __launch_bounds__(kBlock) void dense_knn_kernel(
+    const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc,
+    const int32_t* __restrict__ lab, uint64_t nc, int TC, double thr, int k,
+    int32_t* __restrict__ ids, double* __restrict__ accs, unsigned long long* __restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
+    double* Bs = reinterpret_cast<double*>(smem);                        // [k][QB]
+    T* Qs = reinterpret_cast<T*>(Bs + (size_t)k * QB);                   // [d][QB]
+    T* Cs = Qs + (size_t)d * QB;                                         // [TC][d]
+    int32_t* Li = reinterpret_cast<int32_t*>(Cs + (size_t)TC * d);       // [k][QB]
+    int32_t* Ls = Li + (size_t)k * QB;                                   // [TC]
+    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
+    unsigned nf = 0;
+    for (int e = tid; e < QB * d; e += QB) {
+        const int qr = e / d, ax = e % d;
+        const uint64_t gi = q0 + (uint64_t)qr;
+        const T v = gi < m ? Q[gi * (uint64_t)d + ax] : (T)0;
+        nf += isfinite((double)v) ? 0u : 1u;
+        Qs[(size_t)ax * QB + qr] = v;
+    }
+    if (nf) atomicAdd(bad, (unsigned long long)nf);
+    const uint64_t gi = q0 + (uint64_t)tid;
+    const bool live = gi < m;   // the block's tail lanes sweep nothing and write nothing
+    LdsPairs list;
+    list.init(Bs, Li, tid, QB, k, thr);
+    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
+        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
+        __syncthreads();
+        for (int e = tid; e < tc * d; e += QB)
+            if (PD_OK(t0 * (uint64_t)d + e < nc * (uint64_t)d, 54, t0 * (uint64_t)d + e))
+                Cs[e] = Xc[t0 * (uint64_t)d + e];
+        for (int e = tid; e < tc; e += QB)
+            if (PD_OK(t0 + e < nc, 55, t0 + e)) Ls[e] = lab[t0 + e];
+        __syncthreads();
+        if (!live) continue;
+        for (int c = 0; c < tc; ++c) {
+            const T* cr = Cs + (size_t)c * d;
+            const double tau = list.tau();
+            double acc = 0.0;
+            for (int ax = 0; ax < d; ++ax) {
+                acc = within_axis<M>(acc, (double)Qs[(size_t)ax * QB + tid], (double)cr[ax]);
+                if (acc > tau) break;
+            }
+            if (acc <= tau) list.offer(acc, Ls, (uint32_t)c);
+        }
+    }
+    if (live) {
+        list.order();
+        for (int t = 0; t < k; ++t)
+            knn_store(ids, accs, gi, m, k, t, Bs[(size_t)t * QB + tid], Li[(size_t)t * QB + tid]);
+    }
+}
+
+// An index without rows: every slot (-1, +inf).
+__global__ __launch_bounds__(kBlock) void knn_empty_kernel(int32_t* __restrict__ ids,
+                                                           double* __restrict__ accs,
+                                                           uint64_t total) {
+    const uint64_t w = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (w >= total) return;
+    ids[w] = -1;
+    if (accs) accs[w] = INFINITY;
+}
+
 // ---------------------------------------------------------------- radius query
 // neighbours(q) = every row with acc(q, x) <= thr, thr = fl(radius * radius)
 // (cityblock: radius) for a radius <= the index's eps: the predicate of a train
@@ -1288,6 +1629,111 @@ void kdist_t(Index& ix, const T* Q, uint64_t m, int k, double* out, hipStream_t 
     if (nbad) throw Error(-1, "pd_index_kdist: a query has a NaN or infinite coordinate");
 }
 
+// kdist_launch's tiers at 12 bytes per slot (DESIGN.md §14 has the resource
+// report): registers up to 8; LDS above with kdist's block sizes, so a block's
+// list is at most 48 KiB (256 lanes x 16, 128 x 32, 64 x 64 slots) and three
+// blocks share a CU's 160 KiB: 12, 6 and 3 waves per CU at the top of each tier.
+template <typename T, int D, int M, typename K, int KT>
+void knn_launch(Index& ix, const T* Q, uint64_t m, const uint32_t* order, int k, int lanes,
+                double thr, int32_t* ids, double* acc, unsigned long long* bad, hipStream_t s) {
+    // the LDS list: k pairs per lane and, for the write-out, the lane's query number
+    const size_t lds =
+        KT > 0 ? 0 : (size_t)lanes * (k * (sizeof(double) + sizeof(int32_t)) + sizeof(uint32_t));
+    hipLaunchKernelGGL((knn_kernel<T, D, M, K, KT>), dim3((unsigned)((m + lanes - 1) / lanes)),
+                       dim3(lanes), lds, s, Q, m, order, ix.g, (const T*)ix.Xs, ix.lab, ix.nc,
+                       (const K*)ix.ckey, ix.cstart, ix.tab, ix.ntab, ix.ncells, ix.shift, thr, k,
+                       ids, acc, bad);
+    PD_HIP(hipGetLastError());
+    check_bounds_ix(s, "knn_kernel");
+}
+
+template <typename T, int D, int M, typename K>
+void knn_grid(Index& ix, const T* Q, uint64_t m, int k, double thr, int32_t* ids, double* acc,
+              unsigned long long* bad, hipStream_t s) {
+    const uint32_t* order = query_order<T, D, K>(ix, Q, m, s);
+    if (k <= 4)
+        knn_launch<T, D, M, K, 4>(ix, Q, m, order, k, kBlock, thr, ids, acc, bad, s);
+    else if (k <= 8)
+        knn_launch<T, D, M, K, 8>(ix, Q, m, order, k, kBlock, thr, ids, acc, bad, s);
+    else
+        knn_launch<T, D, M, K, 0>(ix, Q, m, order, k, k <= 16 ? 256 : k <= 32 ? 128 : 64, thr,
+                                  ids, acc, bad, s);
+}
+
+template <typename T, int D, int M>
+void knn_grid_k(Index& ix, const T* Q, uint64_t m, int k, double thr, int32_t* ids, double* acc,
+                unsigned long long* bad, hipStream_t s) {
+    if (ix.key_bytes == 4)
+        knn_grid<T, D, M, uint32_t>(ix, Q, m, k, thr, ids, acc, bad, s);
+    else
+        knn_grid<T, D, M, uint64_t>(ix, Q, m, k, thr, ids, acc, bad, s);
+}
+
+template <typename T, int M>
+void knn_dense(Index& ix, const T* Q, uint64_t m, int k, double thr, int32_t* ids, double* acc,
+               unsigned long long* bad, hipStream_t s) {
+    // kdist_dense's plan with 12 bytes per slot and a label per tile row.  Per
+    // lane: its query row and its k pairs; per block also TC rows and labels.
+    // The block shrinks until its lanes' share is <= 48 KiB (never below 64
+    // lanes); what then passes 60 KiB in all asks for up to 144 KiB through the
+    // function attribute (at most 64 * (944 + 768) = 107 KiB of lanes, which
+    // leaves 39 tile rows of 948 bytes).
+    const size_t row = (size_t)ix.d * sizeof(T);
+    if ((size_t)64 * row + row + 4 > (60u << 10))
+        throw Error(-5, "pd_index_kneighbors: d too large for the tile kernel's LDS (d * itemsize <= 944)");
+    const size_t lane = row + (size_t)k * (sizeof(double) + sizeof(int32_t));
+    int QB = 256;
+    while (QB > 64 && (size_t)QB * lane > (48u << 10)) QB >>= 1;
+    const size_t budget = (size_t)QB * lane + row + 4 <= (60u << 10) ? (60u << 10) : (144u << 10);
+    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * lane) / (row + 4));
+    const size_t lds = (size_t)QB * lane + (size_t)TC * (row + 4);
+    if (lds > (64u << 10))
+        PD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_knn_kernel<T, M>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((dense_knn_kernel<T, M>), dim3((unsigned)((m + QB - 1) / QB)), dim3(QB),
+                       lds, s, Q, m, ix.d, (const T*)ix.Xs, ix.lab, ix.nc, TC, thr, k, ids, acc,
+                       bad);
+    PD_HIP(hipGetLastError());
+    check_bounds_ix(s, "dense_knn_kernel");
+}
+
+template <typename T, int M>
+void knn_m(Index& ix, const T* Q, uint64_t m, int k, int32_t* ids, double* acc,
+           unsigned long long* bad, hipStream_t s) {
+    const double thr = M == 0 ? ix.eps * ix.eps : ix.eps;
+    switch (ix.d) {
+        case 1: knn_grid_k<T, 1, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
+        case 2: knn_grid_k<T, 2, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
+        case 3: knn_grid_k<T, 3, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
+        case 4: knn_grid_k<T, 4, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
+        default: knn_dense<T, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
+    }
+}
+
+// No short cut for an index with fewer than k rows: the walk returns the rows
+// there are.  An index without rows has nothing to walk.
+template <typename T>
+void knn_t(Index& ix, const T* Q, uint64_t m, int k, int32_t* ids, double* acc, hipStream_t s) {
+    Ctx& w = ix.work;
+    unsigned long long* bad = w.arena.get<unsigned long long>("q_bad", 1);
+    PD_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
+    if (ix.nc == 0) {
+        hipLaunchKernelGGL((finite_kernel<T>), dim3(grid_for((int64_t)(m * ix.d), 1024)),
+                           dim3(kBlock), 0, s, Q, m * (uint64_t)ix.d, bad);
+        PD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(knn_empty_kernel, dim3(blocks(m * (uint64_t)k)), dim3(kBlock), 0, s,
+                           ids, acc, m * (uint64_t)k);
+        PD_HIP(hipGetLastError());
+    } else if (ix.metric == 0) {
+        knn_m<T, 0>(ix, Q, m, k, ids, acc, bad, s);
+    } else {
+        knn_m<T, 1>(ix, Q, m, k, ids, acc, bad, s);
+    }
+    unsigned long long nbad = 0;
+    read_u64(w, bad, 1, &nbad, s);
+    if (nbad) throw Error(-1, "pd_index_kneighbors: a query has a NaN or infinite coordinate");
+}
+
 // One pass of a radius query: the count (cnt) or a fill (off, ids, acc, cap).
 struct RadiusCall {
     double thr;
@@ -1446,6 +1892,20 @@ void index_kdist(Index* ix, const void* Q, int dtype, int64_t m, int k, double* 
         kdist_t<float>(*ix, (const float*)Q, (uint64_t)m, k, out, s);
     else
         kdist_t<double>(*ix, (const double*)Q, (uint64_t)m, k, out, s);
+}
+
+void index_kneighbors(Index* ix, const void* Q, int dtype, int64_t m, int k, int32_t* ids,
+                      double* acc, hipStream_t s) {
+    if (k < 1) throw Error(-1, "pd_index_kneighbors: k must be >= 1");
+    if (k > kKdistMaxK) throw Error(-5, "pd_index_kneighbors: k must be <= PD_KDIST_MAX_K (64)");
+    if (dtype != ix->dtype)
+        throw Error(-1, "pd_index_kneighbors: the queries' dtype differs from the index's");
+    if (m >= 0xFFFFFFFFll) throw Error(-5, "pd_index_kneighbors: m must be < 2^32 - 1");
+    if (m == 0) return;
+    if (ix->dtype == 0)
+        knn_t<float>(*ix, (const float*)Q, (uint64_t)m, k, ids, acc, s);
+    else
+        knn_t<double>(*ix, (const double*)Q, (uint64_t)m, k, ids, acc, s);
 }
 
 void index_radius_count(Index* ix, const void* Q, int dtype, int64_t m, double radius,

@@ -364,6 +364,8 @@ Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const
 void index_query(Index* ix, const void* Q, int dtype, int64_t m, int32_t* out, hipStream_t s);
 void index_kdist(Index* ix, const void* Q, int dtype, int64_t m, int k, double* out,
                  hipStream_t s);
+void index_kneighbors(Index* ix, const void* Q, int dtype, int64_t m, int k, int32_t* ids,
+                      double* acc, hipStream_t s);
 void index_radius_count(Index* ix, const void* Q, int dtype, int64_t m, double radius,
                         int64_t* offsets, int64_t* total_host, hipStream_t s);
 void index_radius_fill(Index* ix, const void* Q, int dtype, int64_t m, double radius,

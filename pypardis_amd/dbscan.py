@@ -445,6 +445,74 @@ def radius_neighbors(data, radius, metric='euclidean', queries=None, return_dist
                              count_only)
 
 
+KNeighbors = collections.namedtuple("KNeighbors", ["indices", "distances"])
+
+
+def _kneighbors(X, q, k, r_max, metric, return_distance, squared):
+    """The k nearest rows of ``X`` within ``r_max`` of the rows of ``q``
+    (device tensors): the index over all of X is built, asked once and
+    closed."""
+    if q.shape[1] != X.shape[1]:
+        raise ValueError(f"kneighbors: queries have {q.shape[1]} coordinates, the data "
+                         f"{X.shape[1]}")
+    if q.dtype != X.dtype:
+        q = q.to(X.dtype)
+    try:
+        index = _native.Index.over_rows(X, r_max, metric)
+        try:
+            indices, acc = index.kneighbors(q, k, return_distance)
+        finally:
+            index.close()
+    except _native.PardisError as e:
+        if e.code == _native.PD_EINVAL and "NaN" in str(e):   # sklearn's ValueError
+            raise ValueError(str(e)) from None
+        raise
+    if return_distance and not squared and metric == _native.PD_EUCLIDEAN:
+        acc = torch.sqrt(acc)
+    return KNeighbors(indices, acc)
+
+
+def kneighbors(data, k, r_max, metric='euclidean', queries=None, return_distance=True,
+               squared=False, device=None):
+    """
+    :param data: the indexed points, in any form ``DBSCAN.train`` takes (fewer
+        than 2^31 of them)
+    :param k: how many neighbours (1 <= k <= 64).  A query that is itself a
+        row of ``data`` finds itself first, at distance 0, as everywhere else
+        in this API: for sklearn's ``kneighbors(X=None)``, which leaves the
+        point itself out, ask for k + 1 and drop column 0
+    :param r_max: cap of the search: only rows within ``r_max`` (the
+        predicate of a train at ``eps = r_max``, ties at exactly ``r_max``
+        in) are looked at
+    :param metric: 'euclidean' or 'cityblock' (string or scipy callable)
+    :param queries: the query points (converted to the data's dtype, as in
+        ``predict``); None: the data itself
+    :param return_distance: also return each neighbour's distance
+    :param squared: euclidean only: return the squared distances — the native,
+        bit-reproducible accumulator — instead of their square roots
+    :return: ``KNeighbors(indices, distances)`` of device tensors of shape
+        (m, k) in query order: int32 row numbers of ``data`` and float64
+        distances (None when not asked for).  Each row is ordered by
+        (distance, row number) ascending: among equally distant rows the
+        smaller row number wins and comes first, duplicates each appear.  A
+        query with fewer than k rows within ``r_max`` has its trailing slots
+        at ``-1`` and ``inf``
+
+    Exact: the accumulator is the train's own (fp64, axis order, every product
+    and sum rounded separately) and the order is total, so the result is
+    bit-reproducible and does not depend on the order of the rows beyond the
+    row numbers themselves.  Column k - 1 of the squared distances is
+    ``k_distances(data, k, r_max, squared=True)``.  The cost grows with the
+    number of rows within ``r_max``; 12 bytes per slot are written (4 without
+    the distances).  Single device.
+    """
+    k, r_max = _check_kdist_args(k, r_max)
+    metric = _native.metric_code(metric)
+    X = as_points(data, device).X
+    q = X if queries is None else as_points(queries, X.device).X
+    return _kneighbors(X, q, k, r_max, metric, return_distance, squared)
+
+
 class DBSCAN(object):
     """
     :eps: nearest neighbor radius
@@ -467,7 +535,8 @@ class DBSCAN(object):
     points to the trained clusters, ``fit_predict(data)`` is ``train`` then
     ``labels_``; ``k_distances()`` gives each point's distance to its k-th
     nearest neighbour (the k-distance plot ``eps`` is read from),
-    ``radius_neighbors()`` the eps-graph itself in CSR form.
+    ``radius_neighbors()`` the eps-graph itself in CSR form, ``kneighbors()``
+    each point's k nearest points.
 
     ``sample_weight`` (``train`` / ``fit_predict``; sklearn's ``fit``
     argument): one weight per point; a point is core when the weights of the
@@ -739,6 +808,45 @@ class DBSCAN(object):
         else:
             X = q = as_points(data, self.device).X
         return _k_distances(X, q, k, r_max, metric, squared)
+
+    def kneighbors(self, data=None, k=None, r_max=None, return_distance=True, squared=False):
+        """
+        :param data: query points, in any form ``train`` takes; None: the
+            training points against themselves
+        :param k: default ``min_samples``
+        :param r_max: default ``eps``
+        :return: as the module-level ``kneighbors(points, k, r_max, metric,
+            ...)``, whose other parameters these are: ``KNeighbors(indices,
+            distances)``, (m, k) device tensors, each row ordered by
+            (distance, row number), ``-1`` / ``inf`` where fewer than k points
+            lie within ``r_max``
+
+        A query that is a training point finds itself first, at distance 0
+        (for sklearn's ``kneighbors(X=None)`` ask for k + 1 and drop column
+        0).  After a train the indexed set is the training points, and with
+        the defaults ``core_sample_mask_ == (indices[:, -1] >= 0)``.  Before
+        any train ``data`` is required and is both the indexed set and the
+        queries.  After a ``group=`` train each rank holds only its slice, so
+        ``data=None`` raises; a given ``data`` is then answered against
+        itself.  The index is built and closed per call.
+        """
+        k, r_max = _check_kdist_args(self.min_samples if k is None else k,
+                                     self.eps if r_max is None else r_max)
+        metric = _native.metric_code(self.metric)
+        have = self._points is not None and not self._group_trained
+        if data is None:
+            if self._group_trained:
+                raise ValueError("kneighbors() after a group= train needs data: each rank "
+                                 "holds only its slice of the points")
+            if not have:
+                raise ValueError("kneighbors before train needs data")
+            X = q = self._points.X
+        elif have:
+            X = self._points.X
+            q = as_points(data, X.device).X
+        else:
+            X = q = as_points(data, self.device).X
+        return _kneighbors(X, q, k, r_max, metric, return_distance, squared)
 
     def radius_neighbors(self, data=None, radius=None, return_distance=True, squared=False,
                          sort_results=False, count_only=False):
