@@ -600,7 +600,8 @@ class Index:
         self.eps = float(eps)
         self.n_core = int(nc[0])
 
-    def query(self, Q):
+    def _check_queries(self, Q):
+        """The checks every query method shares; -> the queries' dtype code."""
         if self.ptr is None:
             raise ValueError("the index was closed")
         dt = _check_points(Q)
@@ -608,6 +609,10 @@ class Index:
             raise ValueError(f"queries have {Q.shape[1]} columns, the index was built on {self.d}")
         if Q.device != self.device:
             raise ValueError(f"queries are on {Q.device}, the index on {self.device}")
+        return dt
+
+    def query(self, Q):
+        dt = self._check_queries(Q)
         m = Q.shape[0]
         out = torch.empty(m, dtype=torch.int32, device=Q.device)
         _check(load().pd_index_query(self.ptr, Q.data_ptr() if m else None, dt, m,
@@ -619,13 +624,7 @@ class Index:
         accumulator (squared distance; cityblock: the distance) among the
         index's rows within its ``eps`` of each query, ``inf`` where fewer
         than k are (pd_index_kdist).  1 <= k <= KDIST_MAX_K."""
-        if self.ptr is None:
-            raise ValueError("the index was closed")
-        dt = _check_points(Q)
-        if Q.shape[1] != self.d:
-            raise ValueError(f"queries have {Q.shape[1]} columns, the index was built on {self.d}")
-        if Q.device != self.device:
-            raise ValueError(f"queries are on {Q.device}, the index on {self.device}")
+        dt = self._check_queries(Q)
         m = Q.shape[0]
         out = torch.empty(m, dtype=torch.float64, device=Q.device)
         _check(load().pd_index_kdist(self.ptr, Q.data_ptr() if m else None, dt, m, int(k),
@@ -639,13 +638,7 @@ class Index:
         each row ordered by (acc, label) ascending, ``-1`` / ``inf`` in the
         slots past the rows that qualify (pd_index_kneighbors).  ``acc`` is
         None unless ``return_acc``.  1 <= k <= KDIST_MAX_K."""
-        if self.ptr is None:
-            raise ValueError("the index was closed")
-        dt = _check_points(Q)
-        if Q.shape[1] != self.d:
-            raise ValueError(f"queries have {Q.shape[1]} columns, the index was built on {self.d}")
-        if Q.device != self.device:
-            raise ValueError(f"queries are on {Q.device}, the index on {self.device}")
+        dt = self._check_queries(Q)
         m = Q.shape[0]
         kk = int(k) if 1 <= int(k) <= KDIST_MAX_K else 1   # a bad k is the library's to report
         ids = torch.empty((m, kk), dtype=torch.int32, device=Q.device)
@@ -657,14 +650,7 @@ class Index:
         return ids, acc
 
     def _radius_args(self, Q, radius):
-        if self.ptr is None:
-            raise ValueError("the index was closed")
-        dt = _check_points(Q)
-        if Q.shape[1] != self.d:
-            raise ValueError(f"queries have {Q.shape[1]} columns, the index was built on {self.d}")
-        if Q.device != self.device:
-            raise ValueError(f"queries are on {Q.device}, the index on {self.device}")
-        return dt, float(self.eps if radius is None else radius)
+        return self._check_queries(Q), float(self.eps if radius is None else radius)
 
     def radius_count(self, Q, radius=None):
         """-> (indptr, total): int64 device tensor of m + 1 offsets (the

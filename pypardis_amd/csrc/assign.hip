@@ -44,6 +44,32 @@
 // 64-bit scan of the counts and a fill pass that writes each hit's label —
 // and k-nearest queries (pd_index_kneighbors): the k-distance
 // walk / tiles with a list of (accumulator, label) pairs, written out in order.
+//
+// The four query kinds share one walk and one tile sweep; a
+// kernel is a prologue, a sink, one call and its write-out.  The layers:
+//   view      IxView: what a d <= 4 kernel reads of the index, by value
+//             (view_of fills it from Index)
+//   prologue  QueryAt: lane -> query (through `order`), its coordinates with
+//             the finite check, its cell; a kernel decides what a non-finite
+//             query or one outside the grid gets
+//   rows      for_each_row: the 3^(D-1) rows around the cell, the query's own
+//             first, each as the key run [klo, khi] of its <= 3 cells
+//   run       first_cell / row_run: key run -> occupied cells -> the one record
+//             run [j0, j1) that holds their rows
+//   scan      scan_run: four records' loads and exact sums in flight, offered
+//             to the sink in record order; walk = rows + run + scan
+//   sinks     offer(acc, j) / tau(): RegList, LdsList (k best accumulators),
+//             RegPairs, LdsPairs (k best (acc, label) pairs), RadiusRow (count
+//             or fill), MinLabel (predict, d > 4)
+//   tiles     d > 4: stage_queries (the block's queries transposed into LDS)
+//             and tile_sweep (rows and labels streamed through LDS, the axis
+//             loop that stops at the first partial sum above sink.tau())
+// predict's d <= 4 kernel uses the prologue, the rows and first_cell and keeps
+// its own per-cell loop (labels prune there, and Pred screens in fp32).
+// kdist_kernel calls walk.  knn_kernel and radius_kernel have the walk written
+// out after the shared prologue: through the helpers the first lost occupancy
+// in eight instantiations and the second 0.7 - 1.5 % of its speed (DESIGN.md
+// §15 has the figures).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -339,166 +365,13 @@ struct Rows {
     static constexpr int v = D == 1 ? 1 : D == 2 ? 3 : D == 3 ? 9 : 27;
 };
 
-// One lane per query: the 3^(D-1) neighbour rows, the query's own first, each
-// one key run of <= 3 occupied cells; fp32 screen + exact fp64 recheck (Pred)
-// of the cores whose label could lower the answer; the smallest label among
-// the hits.  order (nullable): lane i sweeps query
-// order[i] (the queries sorted by cell), results go back to input order.
-template <typename T, int D, int M, typename K>
-__global__ __launch_bounds__(kBlock) void query_kernel(
-    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxGrid g,
-    const T* __restrict__ Xs, const int32_t* __restrict__ lab, const K* __restrict__ ckey,
-    const uint32_t* __restrict__ cstart, const int32_t* __restrict__ clab,
-    const uint32_t* __restrict__ tab, uint32_t ncells, int shift, double eps, double eps2, float slo, float shi, int32_t* __restrict__ out,
-    unsigned long long* __restrict__ bad) {
-    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= m) return;
-    const uint64_t qi = order ? (uint64_t)order[i] : i;
-    Pred<T, D, M> pr;
-    bool fin = true;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        pr.ar[j] = Q[qi * D + j];
-        pr.a[j] = (double)pr.ar[j];
-        fin = fin && isfinite(pr.a[j]);
-    }
-    pr.eps = eps;
-    pr.eps2 = eps2;
-    pr.lo = slo;
-    pr.hi = shi;
-    if (!fin) {
-        atomicAdd(bad, 1ull);
-        out[qi] = -1;
-        return;
-    }
-    int64_t c[D];
-    if (!cell_of<D>(pr.a, g, c)) {   // outside the cores' box grown by a cell
-        out[qi] = -1;
-        return;
-    }
-    const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
-    const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
-    int32_t best = INT32_MAX;
-    for (int rq = 0; rq < Rows<D>::v; ++rq) {
-        // the query's own row first: its first hit usually settles every cell
-        // of the same cluster
-        const int r = (rq + Rows<D>::v / 2) % Rows<D>::v;
-        uint64_t base = 0;
-        bool ok = true;
-        int rr = r;
-#pragma unroll
-        for (int a = D - 1; a >= 1; --a) {
-            // r in base 3, axis D-1 the most significant digit
-            int pw = 1;
-            for (int t = 1; t < a; ++t) pw *= 3;
-            const int64_t y = c[a] + (int64_t)(rr / pw) - 1;
-            rr %= pw;
-            ok = ok && y >= 0 && y < g.nc[a];
-            base += (uint64_t)(ok ? y : 0) * g.stride[a];
-        }
-        if (!ok) continue;
-        const uint64_t klo = base + (uint64_t)x0, khi = base + (uint64_t)x1;
-        const uint64_t b = klo >> shift;
-        uint32_t e = cell_lower_bound<K>(ckey, tab[b], tab[b + 1], klo);
-        for (; e < ncells && (uint64_t)ckey[e] <= khi; ++e) {   // <= 3 cells
-            const int32_t cl = clab[e];
-            const uint32_t j1 = cstart[e + 1];
-            uint32_t j = cstart[e];
-            if (cl >= 0) {
-                if (cl >= best) continue;
-                for (; j < j1; ++j) {
-                    T bv[D];
-                    load_raw<T, D>(Xs, j, bv);
-                    if (pr(bv)) {
-                        best = cl;
-                        break;
-                    }
-                }
-            } else {
-                for (; j < j1; ++j) {
-                    const int32_t l = lab[j];
-                    if (l >= best) continue;
-                    T bv[D];
-                    load_raw<T, D>(Xs, j, bv);
-                    if (pr(bv)) best = l;
-                }
-            }
-        }
-    }
-    out[qi] = best == INT32_MAX ? -1 : best;
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void finite_kernel(const T* __restrict__ Q, uint64_t total,
-                                                        unsigned long long* __restrict__ bad) {
-    unsigned c = 0;
-    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < total;
-         e += (uint64_t)gridDim.x * kBlock)
-        c += isfinite((double)Q[e]) ? 0u : 1u;
-    if (c) atomicAdd(bad, (unsigned long long)c);
-}
-
-// d > kMaxDim.  A block of QB lanes owns QB queries, kept transposed in LDS
-// (Qs[k][lane]: conflict-free); the core rows pass through LDS in tiles of TC
-// (every lane reads the same core element: a broadcast).  Each pair runs the
-// predicate's own fp64 sum in axis order (within_axis) and stops at the first
-// partial sum above the threshold — the sum never decreases, so the outcome is
-// that of the full sum.
-template <typename T, int M>
-__global__ __launch_bounds__(kBlock) void dense_query_kernel(
-    const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc,
-    const int32_t* __restrict__ lab, uint64_t nc, int TC, double thr, int32_t* __restrict__ out,
-    unsigned long long* __restrict__ bad) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
-    T* Qs = reinterpret_cast<T*>(smem);
-    T* Cs = Qs + (size_t)d * QB;
-    int32_t* Ls = reinterpret_cast<int32_t*>(Cs + (size_t)TC * d);
-    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
-    unsigned nf = 0;
-    for (int e = tid; e < QB * d; e += QB) {
-        const int row = e / d, k = e % d;
-        const uint64_t gi = q0 + (uint64_t)row;
-        const T v = gi < m ? Q[gi * (uint64_t)d + k] : (T)0;
-        nf += isfinite((double)v) ? 0u : 1u;
-        Qs[(size_t)k * QB + row] = v;
-    }
-    if (nf) atomicAdd(bad, (unsigned long long)nf);
-    int32_t best = INT32_MAX;
-    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
-        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
-        __syncthreads();
-        for (int e = tid; e < tc * d; e += QB) Cs[e] = Xc[t0 * (uint64_t)d + e];
-        for (int e = tid; e < tc; e += QB) Ls[e] = lab[t0 + e];
-        __syncthreads();
-        for (int c = 0; c < tc; ++c) {
-            const T* cr = Cs + (size_t)c * d;
-            double acc = 0.0;
-            for (int k = 0; k < d; ++k) {
-                acc = within_axis<M>(acc, (double)Qs[(size_t)k * QB + tid], (double)cr[k]);
-                if (acc > thr) break;
-            }
-            if (acc <= thr) {
-                const int32_t l = Ls[c];
-                best = l < best ? l : best;
-            }
-        }
-    }
-    const uint64_t gi = q0 + (uint64_t)tid;
-    if (gi < m) out[gi] = best == INT32_MAX ? -1 : best;
-}
-
-// ---------------------------------------------------------------- k-distance
-// kdist(q) = the k-th smallest accumulator (pred.hpp: squared distance, or the
-// cityblock sum) among the rows with acc <= thr, +inf when fewer than k qualify
-// (DESIGN.md §12).  No label prunes a cell here: every candidate of the 3^(D-1)
-// rows gets the exact fp64 accumulator, and what prunes is the moving bound
-// tau = min(thr, k-th best so far), which only the list itself lowers.
-
-// Device-side bounds checks of the k-distance kernels, engine.hip's scheme
+// Device-side bounds checks of the query kernels, engine.hip's scheme
 // (-DPD_CHECK_BOUNDS=1 builds): a checked access that would leave its buffer
 // is skipped and the first one recorded; the host reads the record after the
 // kernel and throws.  Off (the default) PD_OK is `true` and costs nothing.
+// Sites: 40 a query number from `order`; 41 the key prefix into `tab`; 42 a
+// row's record run (covers Xs and lab alike); 43 / 44 a tile's rows / labels;
+// 45 a query's pair of radius offsets; 46 a k-nearest output slot.
 #ifndef PD_CHECK_BOUNDS
 #define PD_CHECK_BOUNDS 0
 #endif
@@ -513,6 +386,313 @@ __device__ __forceinline__ bool pd_ix_ok(bool c, unsigned site, uint64_t idx) {
 #else
 #define PD_OK(cond, site, idx) true
 #endif
+
+// ------------------------------------------------------------ the shared walk
+// What a d <= 4 query kernel reads of the index (view_of fills it).
+template <typename T, typename K>
+struct IxView {
+    IxGrid g;
+    const T* Xs;
+    const int32_t* lab;
+    uint64_t nrec;   // rows of Xs, entries of lab
+    const K* ckey;
+    const uint32_t* cstart;
+    const int32_t* clab;
+    const uint32_t* tab;
+    uint64_t ntab;
+    uint32_t ncells;
+    int shift;
+};
+
+enum Where : int {
+    kPast,        // no query: a lane past m
+    kNonFinite,   // a NaN or infinite coordinate (tallied in `bad`)
+    kOutside,     // more than a cell outside the grid: nothing can be within eps
+    kInGrid
+};
+
+// The prologue of a lane (block of `lanes`): its query — order[i] when the
+// queries are swept in cell order (`order` nullable), results go to row qi of
+// the outputs —, the coordinates as stored and widened, and the cell.
+template <typename T, int D>
+struct QueryAt {
+    uint64_t qi;
+    T ar[D];
+    double a[D];
+    int64_t c[D];   // kInGrid only
+    Where where;
+    __device__ __forceinline__ QueryAt(const T* __restrict__ Q, uint64_t m,
+                                       const uint32_t* __restrict__ order, const IxGrid& g,
+                                       unsigned long long* __restrict__ bad, unsigned lanes) {
+        const uint64_t i = (uint64_t)blockIdx.x * lanes + threadIdx.x;
+        qi = 0;
+        where = kPast;
+        if (i >= m) return;
+        qi = order ? (uint64_t)order[i] : i;
+        if (!PD_OK(qi < m, 40, qi)) return;
+        bool fin = true;
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            ar[j] = Q[qi * D + j];
+            a[j] = (double)ar[j];
+            fin = fin && isfinite(a[j]);
+        }
+        if (!fin) {
+            atomicAdd(bad, 1ull);
+            where = kNonFinite;
+            return;
+        }
+        where = cell_of<D>(a, g, c) ? kInGrid : kOutside;
+    }
+};
+
+// The 3^(D-1) rows of cells around cell c that lie inside the grid, the cell's
+// own row first (its candidates usually settle the rest: predict's first hit,
+// a list's small values): f(klo, khi), the keys of the row's first and last
+// cell (axis 0: c[0] - 1 .. c[0] + 1, clamped).
+template <int D, typename F>
+__device__ __forceinline__ void for_each_row(const IxGrid& g, const int64_t (&c)[D], F&& f) {
+    const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
+    const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
+    for (int rq = 0; rq < Rows<D>::v; ++rq) {
+        const int r = (rq + Rows<D>::v / 2) % Rows<D>::v;
+        uint64_t base = 0;
+        bool ok = true;
+        int rr = r;
+#pragma unroll
+        for (int ax = D - 1; ax >= 1; --ax) {
+            // r in base 3, axis D-1 the most significant digit
+            int pw = 1;
+            for (int t = 1; t < ax; ++t) pw *= 3;
+            const int64_t y = c[ax] + (int64_t)(rr / pw) - 1;
+            rr %= pw;
+            ok = ok && y >= 0 && y < g.nc[ax];
+            base += (uint64_t)(ok ? y : 0) * g.stride[ax];
+        }
+        if (!ok) continue;
+        f(base + (uint64_t)x0, base + (uint64_t)x1);
+    }
+}
+
+// The first occupied cell with a key >= klo: one bucketed binary search.
+template <typename T, typename K>
+__device__ __forceinline__ uint32_t first_cell(const IxView<T, K> v, uint64_t klo) {
+    const uint64_t b = klo >> v.shift;
+    if (!PD_OK(b + 1 < v.ntab, 41, b)) return v.ncells;
+    return cell_lower_bound<K>(v.ckey, v.tab[b], v.tab[b + 1], klo);
+}
+
+// Occupied cells adjacent in ckey hold adjacent records, so the cells of a row
+// are one record run [j0, j1).  False when the row has no occupied cell.
+template <typename T, typename K>
+__device__ __forceinline__ bool row_run(const IxView<T, K> v, uint64_t klo, uint64_t khi,
+                                        uint32_t& j0, uint32_t& j1) {
+    const uint32_t e0 = first_cell(v, klo);
+    uint32_t e1 = e0;
+    for (; e1 < v.ncells && (uint64_t)v.ckey[e1] <= khi; ++e1) {}   // <= 3 cells
+    if (e1 == e0) return false;
+    j0 = v.cstart[e0];
+    j1 = v.cstart[e1];
+    return PD_OK(j0 <= j1 && j1 <= v.nrec, 42, j1);
+}
+
+template <typename T, int D, int M>
+__device__ __forceinline__ double rec_acc(const T* __restrict__ Xs, uint32_t j,
+                                          const double (&a)[D]) {
+    double bv[D];
+    load_rec<T, D>(Xs, j, bv);
+    double acc = 0.0;
+#pragma unroll
+    for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
+    return acc;
+}
+
+// Every record of [j, j1) to the sink, in record order.  Four candidates' loads
+// and sums are issued together (the loads do not wait on the sink).
+template <typename T, int D, int M, typename S>
+__device__ __forceinline__ void scan_run(const T* __restrict__ Xs, const double (&a)[D], uint32_t j,
+                                         uint32_t j1, S& sink) {
+    for (; j + 4 <= j1; j += 4) {
+        double acc4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc4[u] = rec_acc<T, D, M>(Xs, j + u, a);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sink.offer(acc4[u], j + u);
+    }
+    for (; j < j1; ++j) sink.offer(rec_acc<T, D, M>(Xs, j, a), j);
+}
+
+// Every candidate of an in-grid query, with its exact fp64 accumulator, to the
+// sink: sink.offer(acc, j), j the record (lab[j] its label).
+template <typename T, int D, int M, typename K, typename S>
+__device__ __forceinline__ void walk(const IxView<T, K> v, const QueryAt<T, D> q, S& sink) {
+    for_each_row<D>(v.g, q.c, [&](uint64_t klo, uint64_t khi) {
+        uint32_t j0, j1;
+        if (row_run(v, klo, khi, j0, j1)) scan_run<T, D, M>(v.Xs, q.a, j0, j1, sink);
+    });
+}
+
+// predict, d <= 4.  One lane per query; in each row the cells of the key run;
+// fp32 screen + exact fp64 recheck (Pred) of the cores whose label could lower
+// the answer; the smallest label among the hits.
+template <typename T, int D, int M, typename K>
+__global__ __launch_bounds__(kBlock) void query_kernel(
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxView<T, K> v,
+    double eps, double eps2, float slo, float shi, int32_t* __restrict__ out,
+    unsigned long long* __restrict__ bad) {
+    const QueryAt<T, D> q(Q, m, order, v.g, bad, kBlock);
+    if (q.where == kPast) return;
+    if (q.where != kInGrid) {
+        out[q.qi] = -1;
+        return;
+    }
+    Pred<T, D, M> pr;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        pr.ar[j] = q.ar[j];
+        pr.a[j] = q.a[j];
+    }
+    pr.eps = eps;
+    pr.eps2 = eps2;
+    pr.lo = slo;
+    pr.hi = shi;
+    int32_t best = INT32_MAX;
+    for_each_row<D>(v.g, q.c, [&](uint64_t klo, uint64_t khi) {
+        for (uint32_t e = first_cell(v, klo); e < v.ncells && (uint64_t)v.ckey[e] <= khi; ++e) {
+            const int32_t cl = v.clab[e];
+            const uint32_t j1 = v.cstart[e + 1];
+            uint32_t j = v.cstart[e];
+            if (cl >= 0) {
+                if (cl >= best) continue;
+                for (; j < j1; ++j) {
+                    T bv[D];
+                    load_raw<T, D>(v.Xs, j, bv);
+                    if (pr(bv)) {
+                        best = cl;
+                        break;
+                    }
+                }
+            } else {
+                for (; j < j1; ++j) {
+                    const int32_t l = v.lab[j];
+                    if (l >= best) continue;
+                    T bv[D];
+                    load_raw<T, D>(v.Xs, j, bv);
+                    if (pr(bv)) best = l;
+                }
+            }
+        }
+    });
+    out[q.qi] = best == INT32_MAX ? -1 : best;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void finite_kernel(const T* __restrict__ Q, uint64_t total,
+                                                        unsigned long long* __restrict__ bad) {
+    unsigned c = 0;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < total;
+         e += (uint64_t)gridDim.x * kBlock)
+        c += isfinite((double)Q[e]) ? 0u : 1u;
+    if (c) atomicAdd(bad, (unsigned long long)c);
+}
+
+// ------------------------------------------------------------- the tile sweep
+// d > kMaxDim.  A block of QB lanes owns QB queries, kept transposed in LDS
+// (Qs[k][lane]: conflict-free); the rows pass through LDS in tiles of TC
+// (every lane reads the same row element: a broadcast).  Each pair runs the
+// predicate's own fp64 sum in axis order (within_axis) and stops at the first
+// partial sum above the sink's bound — the sum never decreases, so the outcome
+// is that of the full sum, and a pair that is offered ran to the end: its
+// accumulator is the full sum.
+
+// The block's queries into Qs[k][lane] (zero rows past m), non-finite
+// coordinates tallied in `bad`.
+template <typename T>
+__device__ __forceinline__ void stage_queries(const T* __restrict__ Q, uint64_t m, int d, T* Qs,
+                                              unsigned long long* __restrict__ bad) {
+    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
+    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
+    unsigned nf = 0;
+    for (int e = tid; e < QB * d; e += QB) {
+        const int row = e / d, k = e % d;
+        const uint64_t gi = q0 + (uint64_t)row;
+        const T v = gi < m ? Q[gi * (uint64_t)d + k] : (T)0;
+        nf += isfinite((double)v) ? 0u : 1u;
+        Qs[(size_t)k * QB + row] = v;
+    }
+    if (nf) atomicAdd(bad, (unsigned long long)nf);
+}
+
+// Every row of Xc against this lane's staged query: Cs[TC][d] holds the tile,
+// Ls[TC] its labels when the sink reads them (LABELS; it is then given Ls, and
+// j is the row's place in the tile).  A lane that is not `live` keeps the
+// barriers and sweeps nothing.
+template <typename T, int M, bool LABELS, typename S>
+__device__ __forceinline__ void tile_sweep(const T* __restrict__ Xc,
+                                           const int32_t* __restrict__ lab, uint64_t nc, int d,
+                                           int TC, const T* Qs, T* Cs, int32_t* Ls, bool live,
+                                           S& sink) {
+    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
+    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
+        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
+        __syncthreads();
+        for (int e = tid; e < tc * d; e += QB)
+            if (PD_OK(t0 * (uint64_t)d + e < nc * (uint64_t)d, 43, t0 * (uint64_t)d + e))
+                Cs[e] = Xc[t0 * (uint64_t)d + e];
+        if constexpr (LABELS)
+            for (int e = tid; e < tc; e += QB)
+                if (PD_OK(t0 + e < nc, 44, t0 + e)) Ls[e] = lab[t0 + e];
+        __syncthreads();
+        if (!live) continue;
+        for (int c = 0; c < tc; ++c) {
+            const T* cr = Cs + (size_t)c * d;
+            const double tau = sink.tau();
+            double acc = 0.0;
+            for (int ax = 0; ax < d; ++ax) {
+                acc = within_axis<M>(acc, (double)Qs[(size_t)ax * QB + tid], (double)cr[ax]);
+                if (acc > tau) break;
+            }
+            if (acc <= tau) sink.offer(acc, (uint32_t)c);
+        }
+    }
+}
+
+// predict's sink: the smallest label among the cores within thr.
+struct MinLabel {
+    const int32_t* lab;
+    double thr;
+    int32_t best;
+    __device__ __forceinline__ double tau() const { return thr; }
+    __device__ __forceinline__ void offer(double, uint32_t j) {
+        const int32_t l = lab[j];
+        best = l < best ? l : best;
+    }
+};
+
+// predict, d > kMaxDim.  The block's tail lanes sweep a zero row.
+template <typename T, int M>
+__global__ __launch_bounds__(kBlock) void dense_query_kernel(
+    const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc,
+    const int32_t* __restrict__ lab, uint64_t nc, int TC, double thr, int32_t* __restrict__ out,
+    unsigned long long* __restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int QB = (int)blockDim.x;
+    T* Qs = reinterpret_cast<T*>(smem);                                  // [d][QB]
+    T* Cs = Qs + (size_t)d * QB;                                         // [TC][d]
+    int32_t* Ls = reinterpret_cast<int32_t*>(Cs + (size_t)TC * d);       // [TC]
+    stage_queries<T>(Q, m, d, Qs, bad);
+    MinLabel sink{Ls, thr, INT32_MAX};
+    tile_sweep<T, M, true>(Xc, lab, nc, d, TC, Qs, Cs, Ls, true, sink);
+    const uint64_t gi = (uint64_t)blockIdx.x * QB + threadIdx.x;
+    if (gi < m) out[gi] = sink.best == INT32_MAX ? -1 : sink.best;
+}
+
+// ---------------------------------------------------------------- k-distance
+// kdist(q) = the k-th smallest accumulator (pred.hpp: squared distance, or the
+// cityblock sum) among the rows with acc <= thr, +inf when fewer than k qualify
+// (DESIGN.md §12).  No label prunes a cell here: every candidate of the 3^(D-1)
+// rows gets the exact fp64 accumulator, and what prunes is the moving bound
+// tau = min(thr, k-th best so far), which only the list itself lowers.
 
 constexpr int kKdistMaxK = 64;
 
@@ -530,7 +710,7 @@ struct RegList {
 #pragma unroll
         for (int s = 0; s < KT; ++s) b[s] = s < KT - k ? -INFINITY : INFINITY;
     }
-    __device__ __forceinline__ void offer(double acc) {
+    __device__ __forceinline__ void offer(double acc, uint32_t) {
         // tau = min(thr, k-th best): a tie with a full list's last slot changes nothing
         if (!(acc <= thr && acc < b[KT - 1])) return;
 #pragma unroll
@@ -563,7 +743,7 @@ struct LdsList {
         top = -INFINITY;
     }
     __device__ __forceinline__ double tau() const { return cnt < k ? thr : top; }
-    __device__ __forceinline__ void offer(double acc) {
+    __device__ __forceinline__ void offer(double acc, uint32_t) {
         if (cnt < k) {
             if (!(acc <= thr)) return;
             my[(size_t)cnt * stride] = acc;
@@ -587,37 +767,18 @@ struct LdsList {
     __device__ __forceinline__ double result() const { return cnt < k ? (double)INFINITY : top; }
 };
 
-// One lane per query, query_kernel's row walk (own row first, each row one key
-// run of <= 3 occupied cells, `order` for the sorted sweep, the same treatment
-// of queries outside the grid).  KT > 0: the list in registers (k <= KT);
-// KT == 0: in dynamic LDS, k * blockDim.x doubles.
+// d <= 4: the shared walk into a list (the record number is not used).
+// KT > 0: the list in registers (k <= KT); KT == 0: in dynamic LDS,
+// k * blockDim.x doubles.
 template <typename T, int D, int M, typename K, int KT>
 __global__ __launch_bounds__(kBlock) void kdist_kernel(
-    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxGrid g,
-    const T* __restrict__ Xs, uint64_t nrec, const K* __restrict__ ckey,
-    const uint32_t* __restrict__ cstart, const uint32_t* __restrict__ tab, uint64_t ntab,
-    uint32_t ncells, int shift, double thr, int k, double* __restrict__ out,
-    unsigned long long* __restrict__ bad) {
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxView<T, K> v,
+    double thr, int k, double* __restrict__ out, unsigned long long* __restrict__ bad) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const uint64_t qi = order ? (uint64_t)order[i] : i;
-    if (!PD_OK(qi < m, 40, qi)) return;
-    double a[D];
-    bool fin = true;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        a[j] = (double)Q[qi * D + j];
-        fin = fin && isfinite(a[j]);
-    }
-    if (!fin) {
-        atomicAdd(bad, 1ull);
-        out[qi] = INFINITY;
-        return;
-    }
-    int64_t c[D];
-    if (!cell_of<D>(a, g, c)) {   // more than a cell outside the rows' box
-        out[qi] = INFINITY;
+    const QueryAt<T, D> q(Q, m, order, v.g, bad, blockDim.x);
+    if (q.where == kPast) return;
+    if (q.where != kInGrid) {
+        out[q.qi] = INFINITY;
         return;
     }
     typename std::conditional<(KT > 0), RegList<(KT > 0 ? KT : 1)>, LdsList>::type list;
@@ -625,67 +786,12 @@ __global__ __launch_bounds__(kBlock) void kdist_kernel(
         list.init(k, thr);
     else
         list.init(reinterpret_cast<double*>(smem), (int)threadIdx.x, (int)blockDim.x, k, thr);
-    const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
-    const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
-    for (int rq = 0; rq < Rows<D>::v; ++rq) {
-        // the query's own row first: its rows fill the list with small values
-        const int r = (rq + Rows<D>::v / 2) % Rows<D>::v;
-        uint64_t base = 0;
-        bool ok = true;
-        int rr = r;
-#pragma unroll
-        for (int ax = D - 1; ax >= 1; --ax) {
-            int pw = 1;
-            for (int t = 1; t < ax; ++t) pw *= 3;
-            const int64_t y = c[ax] + (int64_t)(rr / pw) - 1;
-            rr %= pw;
-            ok = ok && y >= 0 && y < g.nc[ax];
-            base += (uint64_t)(ok ? y : 0) * g.stride[ax];
-        }
-        if (!ok) continue;
-        const uint64_t klo = base + (uint64_t)x0, khi = base + (uint64_t)x1;
-        const uint64_t b = klo >> shift;
-        if (!PD_OK(b + 1 < ntab, 41, b)) continue;
-        const uint32_t e0 = cell_lower_bound<K>(ckey, tab[b], tab[b + 1], klo);
-        uint32_t e1 = e0;
-        for (; e1 < ncells && (uint64_t)ckey[e1] <= khi; ++e1) {}   // <= 3 cells
-        if (e1 == e0) continue;
-        // occupied cells adjacent in ckey hold adjacent records: the row is one
-        // record run.  Four candidates' loads and sums are issued together (the
-        // loads do not wait on the list), then offered in record order.
-        uint32_t j = cstart[e0];
-        const uint32_t j1 = cstart[e1];
-        if (!PD_OK(j <= j1 && j1 <= nrec, 42, j1)) continue;
-        for (; j + 4 <= j1; j += 4) {
-            double acc4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                double bv[D];
-                load_rec<T, D>(Xs, j + u, bv);
-                double acc = 0.0;
-#pragma unroll
-                for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
-                acc4[u] = acc;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) list.offer(acc4[u]);
-        }
-        for (; j < j1; ++j) {
-            double bv[D];
-            load_rec<T, D>(Xs, j, bv);
-            double acc = 0.0;
-#pragma unroll
-            for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
-            list.offer(acc);
-        }
-    }
-    out[qi] = list.result();
+    walk<T, D, M>(v, q, list);
+    out[q.qi] = list.result();
 }
 
-// d > kMaxDim: dense_query_kernel's tiles (queries transposed in LDS, rows
-// streamed through a tile every lane reads as a broadcast) with each lane's
-// list in LDS next to them.  The axis loop stops at the first partial sum
-// above tau: the sum never decreases, so such a pair could not enter the list.
+// d > kMaxDim: the tile sweep with each lane's list in LDS next to the tiles.
+// The block's tail lanes sweep a zero row.
 template <typename T, int M>
 __global__ __launch_bounds__(kBlock) void dense_kdist_kernel(
     const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc, uint64_t nc, int TC,
@@ -695,37 +801,11 @@ __global__ __launch_bounds__(kBlock) void dense_kdist_kernel(
     double* Bs = reinterpret_cast<double*>(smem);            // [k][QB]
     T* Qs = reinterpret_cast<T*>(Bs + (size_t)k * QB);       // [d][QB]
     T* Cs = Qs + (size_t)d * QB;                             // [TC][d]
-    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
-    unsigned nf = 0;
-    for (int e = tid; e < QB * d; e += QB) {
-        const int row = e / d, ax = e % d;
-        const uint64_t gi = q0 + (uint64_t)row;
-        const T v = gi < m ? Q[gi * (uint64_t)d + ax] : (T)0;
-        nf += isfinite((double)v) ? 0u : 1u;
-        Qs[(size_t)ax * QB + row] = v;
-    }
-    if (nf) atomicAdd(bad, (unsigned long long)nf);
+    stage_queries<T>(Q, m, d, Qs, bad);
     LdsList list;
     list.init(Bs, tid, QB, k, thr);
-    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
-        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
-        __syncthreads();
-        for (int e = tid; e < tc * d; e += QB)
-            if (PD_OK(t0 * (uint64_t)d + e < nc * (uint64_t)d, 43, t0 * (uint64_t)d + e))
-                Cs[e] = Xc[t0 * (uint64_t)d + e];
-        __syncthreads();
-        for (int c = 0; c < tc; ++c) {
-            const T* cr = Cs + (size_t)c * d;
-            const double tau = list.tau();
-            double acc = 0.0;
-            for (int ax = 0; ax < d; ++ax) {
-                acc = within_axis<M>(acc, (double)Qs[(size_t)ax * QB + tid], (double)cr[ax]);
-                if (acc > tau) break;
-            }
-            if (acc <= tau) list.offer(acc);
-        }
-    }
-    const uint64_t gi = q0 + (uint64_t)tid;
+    tile_sweep<T, M, false>(Xc, nullptr, nc, d, TC, Qs, Cs, nullptr, true, list);
+    const uint64_t gi = (uint64_t)blockIdx.x * QB + (uint64_t)tid;
     if (gi < m) out[gi] = list.result();
 }
 
@@ -754,7 +834,7 @@ __device__ __forceinline__ void knn_store(int32_t* __restrict__ ids, double* __r
                                           uint64_t qi, uint64_t m, int k, int t, double acc,
                                           int32_t l) {
     const uint64_t w = qi * (uint64_t)k + (uint64_t)t;   // m * k passes 2^31 (C2: from k = 22)
-    if (!PD_OK(w < m * (uint64_t)k, 53, w)) return;
+    if (!PD_OK(w < m * (uint64_t)k, 46, w)) return;
     const bool none = !(acc < INFINITY);
     ids[w] = none ? -1 : l;
     if (accs) accs[w] = none ? (double)INFINITY : acc;
@@ -770,7 +850,9 @@ struct RegPairs {
     double b[KT];
     int32_t l[KT];
     double thr;
-    __device__ __forceinline__ void init(int k, double thr_) {
+    const int32_t* lab;   // lab[j]: candidate j's label
+    __device__ __forceinline__ void init(const int32_t* lab_, int k, double thr_) {
+        lab = lab_;
         thr = thr_;
 #pragma unroll
         for (int s = 0; s < KT; ++s) {
@@ -779,8 +861,8 @@ struct RegPairs {
         }
     }
     __device__ __forceinline__ double tau() const { return thr < b[KT - 1] ? thr : b[KT - 1]; }
-    // lab[j]: the candidate's label, read only once acc has passed tau
-    __device__ __forceinline__ void offer(double acc, const int32_t* __restrict__ lab, uint32_t j) {
+    // the candidate's label is read only once acc has passed tau
+    __device__ __forceinline__ void offer(double acc, uint32_t j) {
         if (!(acc <= thr && acc <= b[KT - 1])) return;
         const int32_t la = lab[j];
         if (!pair_lt(acc, la, b[KT - 1], l[KT - 1])) return;
@@ -816,8 +898,10 @@ struct LdsPairs {
     int k, cnt, imax;
     double thr, top;  // (top, ltop): largest pair so far
     int32_t ltop;
-    __device__ __forceinline__ void init(double* base, int32_t* lbase, int lane, int lanes, int k_,
-                                         double thr_) {
+    const int32_t* lab;   // lab[j]: candidate j's label
+    __device__ __forceinline__ void init(const int32_t* lab_, double* base, int32_t* lbase, int lane,
+                                         int lanes, int k_, double thr_) {
+        lab = lab_;
         my = base + lane;
         myl = lbase + lane;
         stride = lanes;
@@ -829,7 +913,7 @@ struct LdsPairs {
         ltop = INT32_MIN;
     }
     __device__ __forceinline__ double tau() const { return cnt < k ? thr : top; }
-    __device__ __forceinline__ void offer(double acc, const int32_t* __restrict__ lab, uint32_t j) {
+    __device__ __forceinline__ void offer(double acc, uint32_t j) {
         if (!(acc <= tau())) return;
         const int32_t la = lab[j];
         if (cnt < k) {
@@ -888,54 +972,42 @@ struct LdsPairs {
     }
 };
 
-// kdist_kernel's walk (one lane per query, its own row first, each row one
-// record run, four candidates' loads and sums in flight, `order` for the
-// cell-sorted sweep) over a pair list.  KT > 0: in registers (k <= KT), each
-// lane stores its own row.  KT == 0: in dynamic LDS — k * blockDim.x doubles,
-// as many int32, a query number per lane — where each lane orders its row and
-// the block then stores the rows side by side (C2, k = 10, ids + acc of all
-// points: 80.7 -> 75.4 ms against each lane storing its own).  A non-finite
-// query and one more than a cell outside the grid keep an empty list: k slots
-// of (-1, +inf).
+// d <= 4: the walk into a pair list, after the shared prologue.  KT > 0: in
+// registers (k <= KT), each lane stores its own row.  KT == 0: in dynamic LDS —
+// k * blockDim.x doubles, as many int32, a query number per lane — where each
+// lane orders its row and the block then stores the rows side by side (C2,
+// k = 10, ids + acc of all points: 80.7 -> 75.4 ms against each lane storing
+// its own); those rows leave through a barrier, so no lane of that tier exits
+// early.  A non-finite query and one more than a cell outside the grid keep an
+// empty list: k slots of (-1, +inf).
 template <typename T, int D, int M, typename K, int KT>
 __global__ __launch_bounds__(kBlock) void knn_kernel(
-    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxGrid g,
-    const T* __restrict__ Xs, const int32_t* __restrict__ lab, uint64_t nrec,
-    const K* __restrict__ ckey, const uint32_t* __restrict__ cstart,
-    const uint32_t* __restrict__ tab, uint64_t ntab, uint32_t ncells, int shift, double thr, int k,
-    int32_t* __restrict__ ids, double* __restrict__ accs, unsigned long long* __restrict__ bad) {
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxView<T, K> v,
+    double thr, int k, int32_t* __restrict__ ids, double* __restrict__ accs,
+    unsigned long long* __restrict__ bad) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr bool kLds = KT == 0;   // its rows leave through a barrier: no lane exits early
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (!kLds && i >= m) return;
-    bool live = i < m;
-    const uint64_t qi = live ? (order ? (uint64_t)order[i] : i) : 0;
-    if (!PD_OK(qi < m, 50, qi)) {
-        if (!kLds) return;
-        live = false;
-    }
-    double a[D];
-    bool fin = live;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        a[j] = live ? (double)Q[qi * D + j] : 0.0;
-        fin = fin && isfinite(a[j]);
-    }
-    if (live && !fin) atomicAdd(bad, 1ull);
+    constexpr bool kLds = KT == 0;
+    const QueryAt<T, D> q(Q, m, order, v.g, bad, blockDim.x);
+    if (!kLds && q.where == kPast) return;
     typename std::conditional<(KT > 0), RegPairs<(KT > 0 ? KT : 1)>, LdsPairs>::type list;
     if constexpr (KT > 0) {
-        list.init(k, thr);
+        list.init(v.lab, k, thr);
     } else {
         double* Bs = reinterpret_cast<double*>(smem);
-        list.init(Bs, reinterpret_cast<int32_t*>(Bs + (size_t)k * blockDim.x), (int)threadIdx.x,
-                  (int)blockDim.x, k, thr);
+        list.init(v.lab, Bs, reinterpret_cast<int32_t*>(Bs + (size_t)k * blockDim.x),
+                  (int)threadIdx.x, (int)blockDim.x, k, thr);
     }
-    int64_t c[D];
-    if (fin && cell_of<D>(a, g, c)) {
+    // The walk (for_each_row + row_run + scan_run) written out: through the
+    // shared helpers the register pair lists of d = 1 lose a wave of occupancy,
+    // and with only the scan written out k = 10 over all of C2 is 0.2 % slower
+    // (DESIGN.md §15).  Keep it in step with them.
+    if (q.where == kInGrid) {
+        const IxGrid& g = v.g;
+        const int64_t (&c)[D] = q.c;
+        const double (&a)[D] = q.a;
         const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
         const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
         for (int rq = 0; rq < Rows<D>::v; ++rq) {
-            // the query's own row first: its rows fill the list with small values
             const int r = (rq + Rows<D>::v / 2) % Rows<D>::v;
             uint64_t base = 0;
             bool in = true;
@@ -951,36 +1023,36 @@ __global__ __launch_bounds__(kBlock) void knn_kernel(
             }
             if (!in) continue;
             const uint64_t klo = base + (uint64_t)x0, khi = base + (uint64_t)x1;
-            const uint64_t b = klo >> shift;
-            if (!PD_OK(b + 1 < ntab, 51, b)) continue;
-            const uint32_t e0 = cell_lower_bound<K>(ckey, tab[b], tab[b + 1], klo);
+            const uint64_t b = klo >> v.shift;
+            if (!PD_OK(b + 1 < v.ntab, 41, b)) continue;
+            const uint32_t e0 = cell_lower_bound<K>(v.ckey, v.tab[b], v.tab[b + 1], klo);
             uint32_t e1 = e0;
-            for (; e1 < ncells && (uint64_t)ckey[e1] <= khi; ++e1) {}   // <= 3 cells
+            for (; e1 < v.ncells && (uint64_t)v.ckey[e1] <= khi; ++e1) {}   // <= 3 cells
             if (e1 == e0) continue;
-            uint32_t j = cstart[e0];
-            const uint32_t j1 = cstart[e1];
-            if (!PD_OK(j <= j1 && j1 <= nrec, 52, j1)) continue;   // covers Xs and lab alike
+            uint32_t j = v.cstart[e0];
+            const uint32_t j1 = v.cstart[e1];
+            if (!PD_OK(j <= j1 && j1 <= v.nrec, 42, j1)) continue;
             for (; j + 4 <= j1; j += 4) {
                 double acc4[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     double bv[D];
-                    load_rec<T, D>(Xs, j + u, bv);
+                    load_rec<T, D>(v.Xs, j + u, bv);
                     double acc = 0.0;
 #pragma unroll
                     for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
                     acc4[u] = acc;
                 }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) list.offer(acc4[u], lab, j + u);
+                for (int u = 0; u < 4; ++u) list.offer(acc4[u], j + u);
             }
             for (; j < j1; ++j) {
                 double bv[D];
-                load_rec<T, D>(Xs, j, bv);
+                load_rec<T, D>(v.Xs, j, bv);
                 double acc = 0.0;
 #pragma unroll
                 for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
-                list.offer(acc, lab, j);
+                list.offer(acc, j);
             }
         }
     }
@@ -992,24 +1064,24 @@ __global__ __launch_bounds__(kBlock) void knn_kernel(
         int32_t* Li = reinterpret_cast<int32_t*>(Bs + (size_t)k * lanes);
         uint32_t* Qi = reinterpret_cast<uint32_t*>(Li + (size_t)k * lanes);
         list.order();
-        Qi[tid] = live ? (uint32_t)qi : 0xFFFFFFFFu;   // m < 2^32 - 1
+        Qi[tid] = q.where != kPast ? (uint32_t)q.qi : 0xFFFFFFFFu;   // m < 2^32 - 1
         __syncthreads();
         for (int e = tid; e < lanes * k; e += lanes) {
             const int rl = e / k, t = e - rl * k;
-            const uint32_t q = Qi[rl];
-            if (q != 0xFFFFFFFFu)
-                knn_store(ids, accs, (uint64_t)q, m, k, t, Bs[(size_t)t * lanes + rl],
+            const uint32_t qr = Qi[rl];
+            if (qr != 0xFFFFFFFFu)
+                knn_store(ids, accs, (uint64_t)qr, m, k, t, Bs[(size_t)t * lanes + rl],
                           Li[(size_t)t * lanes + rl]);
         }
     } else {
-        list.write(ids, accs, qi, m, k);
+        list.write(ids, accs, q.qi, m, k);
     }
 }
 
-// d > kMaxDim: dense_kdist_kernel's tiles with the rows' labels streamed beside
-// them (as dense_radius_kernel's fill) and each lane's pair list in LDS.  The
-// axis loop stops at the first partial sum above tau; a sum equal to tau runs
-// to the end and is offered, where its label decides.
+// d > kMaxDim: the tile sweep with the rows' labels streamed beside them and
+// each lane's pair list in LDS.  A sum equal to tau runs to the end and is
+// offered, where its label decides.  The block's tail lanes sweep nothing and
+// write nothing.
 template <typename T, int M>
 __global__ __launch_bounds__(kBlock) void dense_knn_kernel(
     const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc,
@@ -1022,41 +1094,12 @@ __global__ __launch_bounds__(kBlock) void dense_knn_kernel(
     T* Cs = Qs + (size_t)d * QB;                                         // [TC][d]
     int32_t* Li = reinterpret_cast<int32_t*>(Cs + (size_t)TC * d);       // [k][QB]
     int32_t* Ls = Li + (size_t)k * QB;                                   // [TC]
-    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
-    unsigned nf = 0;
-    for (int e = tid; e < QB * d; e += QB) {
-        const int qr = e / d, ax = e % d;
-        const uint64_t gi = q0 + (uint64_t)qr;
-        const T v = gi < m ? Q[gi * (uint64_t)d + ax] : (T)0;
-        nf += isfinite((double)v) ? 0u : 1u;
-        Qs[(size_t)ax * QB + qr] = v;
-    }
-    if (nf) atomicAdd(bad, (unsigned long long)nf);
-    const uint64_t gi = q0 + (uint64_t)tid;
-    const bool live = gi < m;   // the block's tail lanes sweep nothing and write nothing
+    stage_queries<T>(Q, m, d, Qs, bad);
+    const uint64_t gi = (uint64_t)blockIdx.x * QB + (uint64_t)tid;
+    const bool live = gi < m;
     LdsPairs list;
-    list.init(Bs, Li, tid, QB, k, thr);
-    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
-        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
-        __syncthreads();
-        for (int e = tid; e < tc * d; e += QB)
-            if (PD_OK(t0 * (uint64_t)d + e < nc * (uint64_t)d, 54, t0 * (uint64_t)d + e))
-                Cs[e] = Xc[t0 * (uint64_t)d + e];
-        for (int e = tid; e < tc; e += QB)
-            if (PD_OK(t0 + e < nc, 55, t0 + e)) Ls[e] = lab[t0 + e];
-        __syncthreads();
-        if (!live) continue;
-        for (int c = 0; c < tc; ++c) {
-            const T* cr = Cs + (size_t)c * d;
-            const double tau = list.tau();
-            double acc = 0.0;
-            for (int ax = 0; ax < d; ++ax) {
-                acc = within_axis<M>(acc, (double)Qs[(size_t)ax * QB + tid], (double)cr[ax]);
-                if (acc > tau) break;
-            }
-            if (acc <= tau) list.offer(acc, Ls, (uint32_t)c);
-        }
-    }
+    list.init(Ls, Bs, Li, tid, QB, k, thr);
+    tile_sweep<T, M, true>(Xc, lab, nc, d, TC, Qs, Cs, Ls, live, list);
     if (live) {
         list.order();
         for (int t = 0; t < k; ++t)
@@ -1091,11 +1134,20 @@ __global__ __launch_bounds__(kBlock) void knn_empty_kernel(int32_t* __restrict__
 // an error code, never as a stray store.
 template <int FILL>
 struct RadiusRow {
+    double thr;
+    const int32_t* lab;     // FILL: lab[j] is candidate j's label
+    int32_t* ids;
+    double* accs;
     uint32_t n;             // hits so far
     int64_t pos, end, lim;  // FILL: stores go to [pos, lim)
     bool ok;
-    __device__ __forceinline__ void open(const int64_t* __restrict__ off, uint64_t qi, uint64_t m,
-                                         int64_t cap) {
+    __device__ __forceinline__ void open(double thr_, const int32_t* lab_,
+                                         const int64_t* __restrict__ off, int32_t* ids_,
+                                         double* accs_, uint64_t qi, uint64_t m, int64_t cap) {
+        thr = thr_;
+        lab = lab_;
+        ids = ids_;
+        accs = accs_;
         n = 0;
         if constexpr (FILL > 0) {
             ok = PD_OK(qi + 1 <= m, 45, qi);
@@ -1106,9 +1158,8 @@ struct RadiusRow {
             lim = ok ? (end < cap ? end : cap) : 0;
         }
     }
-    __device__ __forceinline__ void offer(double acc, double thr, const int32_t* __restrict__ lab,
-                                          uint32_t j, int32_t* __restrict__ ids,
-                                          double* __restrict__ accs) {
+    __device__ __forceinline__ double tau() const { return thr; }
+    __device__ __forceinline__ void offer(double acc, uint32_t j) {
         if (!(acc <= thr)) return;
         if constexpr (FILL > 0) {
             const int64_t w = pos + (int64_t)n;   // pos <= cap: no overflow
@@ -1129,35 +1180,27 @@ struct RadiusRow {
     }
 };
 
-// d <= 4: kdist_kernel's walk without the list — one lane per query, its own
-// row first, each row one contiguous record run, four candidates' loads and
-// sums in flight, `order` for the cell-sorted sweep, nothing for a query more
-// than a cell outside the grid.  Hits keep the walk's order, which a given
-// index and call fix.  tally[0]: non-finite queries; tally[1]: see RadiusRow.
+// d <= 4: the walk into a RadiusRow, after the shared prologue; nothing for a
+// non-finite query or one more than a cell outside the grid.  Hits keep the
+// walk's order, which a given index and call fix.  tally[0]: non-finite
+// queries; tally[1]: see RadiusRow.
 template <typename T, int D, int M, typename K, int FILL>
 __global__ __launch_bounds__(kBlock) void radius_kernel(
-    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxGrid g,
-    const T* __restrict__ Xs, const int32_t* __restrict__ lab, uint64_t nrec,
-    const K* __restrict__ ckey, const uint32_t* __restrict__ cstart,
-    const uint32_t* __restrict__ tab, uint64_t ntab, uint32_t ncells, int shift, double thr,
-    uint32_t* __restrict__ cnt, const int64_t* __restrict__ off, int32_t* __restrict__ ids,
-    double* __restrict__ accs, int64_t cap, unsigned long long* __restrict__ tally) {
-    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= m) return;
-    const uint64_t qi = order ? (uint64_t)order[i] : i;
-    if (!PD_OK(qi < m, 44, qi)) return;
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxView<T, K> v,
+    double thr, uint32_t* __restrict__ cnt, const int64_t* __restrict__ off,
+    int32_t* __restrict__ ids, double* __restrict__ accs, int64_t cap,
+    unsigned long long* __restrict__ tally) {
+    const QueryAt<T, D> q(Q, m, order, v.g, tally, kBlock);
+    if (q.where == kPast) return;
     RadiusRow<FILL> row;
-    row.open(off, qi, m, cap);
-    double a[D];
-    bool fin = true;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        a[j] = (double)Q[qi * D + j];
-        fin = fin && isfinite(a[j]);
-    }
-    if (!fin) atomicAdd(tally, 1ull);
-    int64_t c[D];
-    if (fin && cell_of<D>(a, g, c)) {
+    row.open(thr, v.lab, off, ids, accs, q.qi, m, cap);
+    // The walk (for_each_row + row_run + scan_run) written out: through the
+    // shared helpers the passes over all of C2 are 0.7 - 1.5 % slower (DESIGN.md
+    // §15).  Keep it in step with them.
+    if (q.where == kInGrid) {
+        const IxGrid& g = v.g;
+        const int64_t (&c)[D] = q.c;
+        const double (&a)[D] = q.a;
         const int64_t x0 = c[0] - 1 < 0 ? 0 : c[0] - 1;
         const int64_t x1 = c[0] + 1 >= g.nc[0] ? g.nc[0] - 1 : c[0] + 1;
         for (int rq = 0; rq < Rows<D>::v; ++rq) {
@@ -1176,46 +1219,44 @@ __global__ __launch_bounds__(kBlock) void radius_kernel(
             }
             if (!in) continue;
             const uint64_t klo = base + (uint64_t)x0, khi = base + (uint64_t)x1;
-            const uint64_t b = klo >> shift;
-            if (!PD_OK(b + 1 < ntab, 46, b)) continue;
-            const uint32_t e0 = cell_lower_bound<K>(ckey, tab[b], tab[b + 1], klo);
+            const uint64_t b = klo >> v.shift;
+            if (!PD_OK(b + 1 < v.ntab, 41, b)) continue;
+            const uint32_t e0 = cell_lower_bound<K>(v.ckey, v.tab[b], v.tab[b + 1], klo);
             uint32_t e1 = e0;
-            for (; e1 < ncells && (uint64_t)ckey[e1] <= khi; ++e1) {}   // <= 3 cells
+            for (; e1 < v.ncells && (uint64_t)v.ckey[e1] <= khi; ++e1) {}   // <= 3 cells
             if (e1 == e0) continue;
-            uint32_t j = cstart[e0];
-            const uint32_t j1 = cstart[e1];
-            if (!PD_OK(j <= j1 && j1 <= nrec, 47, j1)) continue;
+            uint32_t j = v.cstart[e0];
+            const uint32_t j1 = v.cstart[e1];
+            if (!PD_OK(j <= j1 && j1 <= v.nrec, 42, j1)) continue;
             for (; j + 4 <= j1; j += 4) {
                 double acc4[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     double bv[D];
-                    load_rec<T, D>(Xs, j + u, bv);
+                    load_rec<T, D>(v.Xs, j + u, bv);
                     double acc = 0.0;
 #pragma unroll
                     for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
                     acc4[u] = acc;
                 }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) row.offer(acc4[u], thr, lab, j + u, ids, accs);
+                for (int u = 0; u < 4; ++u) row.offer(acc4[u], j + u);
             }
             for (; j < j1; ++j) {
                 double bv[D];
-                load_rec<T, D>(Xs, j, bv);
+                load_rec<T, D>(v.Xs, j, bv);
                 double acc = 0.0;
 #pragma unroll
                 for (int ax = 0; ax < D; ++ax) acc = within_axis<M>(acc, a[ax], bv[ax]);
-                row.offer(acc, thr, lab, j, ids, accs);
+                row.offer(acc, j);
             }
         }
     }
-    row.close(cnt, qi, cap, tally);
+    row.close(cnt, q.qi, cap, tally);
 }
 
-// d > kMaxDim: dense_query_kernel's tiles (queries transposed in LDS, rows and
-// — for a fill — their labels streamed through a tile every lane reads as a
-// broadcast).  The axis loop stops at the first partial sum above thr; a pair
-// that is accepted ran it to the end, so its accumulator is the full sum.
+// d > kMaxDim: the tile sweep into a RadiusRow, the rows' labels streamed beside
+// them for a fill.  The block's tail lanes sweep nothing and emit nothing.
 template <typename T, int M, int FILL>
 __global__ __launch_bounds__(kBlock) void dense_radius_kernel(
     const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc,
@@ -1223,45 +1264,16 @@ __global__ __launch_bounds__(kBlock) void dense_radius_kernel(
     const int64_t* __restrict__ off, int32_t* __restrict__ ids, double* __restrict__ accs,
     int64_t cap, unsigned long long* __restrict__ tally) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
+    const int QB = (int)blockDim.x;
     T* Qs = reinterpret_cast<T*>(smem);                                  // [d][QB]
     T* Cs = Qs + (size_t)d * QB;                                         // [TC][d]
     int32_t* Ls = reinterpret_cast<int32_t*>(Cs + (size_t)TC * d);       // [TC]
-    const uint64_t q0 = (uint64_t)blockIdx.x * QB;
-    unsigned nf = 0;
-    for (int e = tid; e < QB * d; e += QB) {
-        const int qr = e / d, ax = e % d;
-        const uint64_t gi = q0 + (uint64_t)qr;
-        const T v = gi < m ? Q[gi * (uint64_t)d + ax] : (T)0;
-        nf += isfinite((double)v) ? 0u : 1u;
-        Qs[(size_t)ax * QB + qr] = v;
-    }
-    if (nf) atomicAdd(tally, (unsigned long long)nf);
-    const uint64_t gi = q0 + (uint64_t)tid;
-    const bool live = gi < m;   // the block's tail lanes sweep a zero row and emit nothing
+    stage_queries<T>(Q, m, d, Qs, tally);
+    const uint64_t gi = (uint64_t)blockIdx.x * QB + threadIdx.x;
+    const bool live = gi < m;
     RadiusRow<FILL> row;
-    row.open(off, live ? gi : 0, m, cap);
-    for (uint64_t t0 = 0; t0 < nc; t0 += (uint64_t)TC) {
-        const int tc = (int)(nc - t0 < (uint64_t)TC ? nc - t0 : (uint64_t)TC);
-        __syncthreads();
-        for (int e = tid; e < tc * d; e += QB)
-            if (PD_OK(t0 * (uint64_t)d + e < nc * (uint64_t)d, 48, t0 * (uint64_t)d + e))
-                Cs[e] = Xc[t0 * (uint64_t)d + e];
-        if constexpr (FILL > 0)
-            for (int e = tid; e < tc; e += QB)
-                if (PD_OK(t0 + e < nc, 49, t0 + e)) Ls[e] = lab[t0 + e];
-        __syncthreads();
-        if (!live) continue;
-        for (int c = 0; c < tc; ++c) {
-            const T* cr = Cs + (size_t)c * d;
-            double acc = 0.0;
-            for (int ax = 0; ax < d; ++ax) {
-                acc = within_axis<M>(acc, (double)Qs[(size_t)ax * QB + tid], (double)cr[ax]);
-                if (acc > thr) break;
-            }
-            row.offer(acc, thr, Ls, (uint32_t)c, ids, accs);
-        }
-    }
+    row.open(thr, Ls, off, ids, accs, live ? gi : 0, m, cap);
+    tile_sweep<T, M, (FILL > 0)>(Xc, lab, nc, d, TC, Qs, Cs, Ls, live, row);
     if (live) row.close(cnt, gi, cap, tally);
 }
 
@@ -1272,7 +1284,7 @@ __global__ __launch_bounds__(kBlock) void radius_empty_kernel(const int64_t* __r
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= m) return;
     RadiusRow<1> row;
-    row.open(off, i, m, cap);
+    row.open(0.0, nullptr, off, nullptr, nullptr, i, m, cap);
     row.close(nullptr, i, cap, tally);
 }
 
@@ -1443,75 +1455,14 @@ const uint32_t* query_order(Index& ix, const T* Q, uint64_t m, hipStream_t s) {
     return vals;
 }
 
-template <typename T, int D, int M, typename K>
-void query_grid(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
-                hipStream_t s) {
-    const uint32_t* order = query_order<T, D, K>(ix, Q, m, s);
-    hipLaunchKernelGGL((query_kernel<T, D, M, K>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m, order,
-                       ix.g, (const T*)ix.Xs, ix.lab, (const K*)ix.ckey, ix.cstart, ix.clab, ix.tab,
-                       ix.ncells, ix.shift, ix.eps, ix.eps * ix.eps, ix.slo, ix.shi, out, bad);
-    PD_HIP(hipGetLastError());
+template <typename T, typename K>
+IxView<T, K> view_of(const Index& ix) {
+    return {ix.g,    (const T*)ix.Xs, ix.lab,   ix.nc,     (const K*)ix.ckey, ix.cstart,
+            ix.clab, ix.tab,          ix.ntab,  ix.ncells, ix.shift};
 }
 
-template <typename T, int D, int M>
-void query_grid_k(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
-                  hipStream_t s) {
-    if (ix.key_bytes == 4)
-        query_grid<T, D, M, uint32_t>(ix, Q, m, out, bad, s);
-    else
-        query_grid<T, D, M, uint64_t>(ix, Q, m, out, bad, s);
-}
-
-template <typename T, int M>
-void query_dense(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
-                 hipStream_t s) {
-    // LDS: QB query rows (<= 32 KiB where a block size allows it) + TC core
-    // rows and labels, 60 KiB in all
-    const size_t row = (size_t)ix.d * sizeof(T);
-    int QB = 256;
-    while (QB > 64 && (size_t)QB * row > (32u << 10)) QB >>= 1;
-    const size_t budget = 60u << 10;
-    if ((size_t)QB * row + row + 4 > budget)
-        throw Error(-5, "pd_index_query: d too large for the tile kernel's LDS (d * itemsize <= 944)");
-    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * row) / (row + 4));
-    const size_t lds = (size_t)QB * row + (size_t)TC * (row + 4);
-    const double thr = M == 0 ? ix.eps * ix.eps : ix.eps;
-    hipLaunchKernelGGL((dense_query_kernel<T, M>), dim3((unsigned)((m + QB - 1) / QB)), dim3(QB),
-                       lds, s, Q, m, ix.d, (const T*)ix.Xs, ix.lab, ix.nc, TC, thr, out, bad);
-    PD_HIP(hipGetLastError());
-}
-
-template <typename T, int M>
-void query_m(Index& ix, const T* Q, uint64_t m, int32_t* out, unsigned long long* bad,
-             hipStream_t s) {
-    switch (ix.d) {
-        case 1: query_grid_k<T, 1, M>(ix, Q, m, out, bad, s); break;
-        case 2: query_grid_k<T, 2, M>(ix, Q, m, out, bad, s); break;
-        case 3: query_grid_k<T, 3, M>(ix, Q, m, out, bad, s); break;
-        case 4: query_grid_k<T, 4, M>(ix, Q, m, out, bad, s); break;
-        default: query_dense<T, M>(ix, Q, m, out, bad, s); break;
-    }
-}
-
-template <typename T>
-void query_t(Index& ix, const T* Q, uint64_t m, int32_t* out, hipStream_t s) {
-    Ctx& w = ix.work;
-    unsigned long long* bad = w.arena.get<unsigned long long>("q_bad", 1);
-    PD_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
-    if (ix.nc == 0) {
-        hipLaunchKernelGGL((finite_kernel<T>), dim3(grid_for((int64_t)(m * ix.d), 1024)),
-                           dim3(kBlock), 0, s, Q, m * (uint64_t)ix.d, bad);
-        PD_HIP(hipGetLastError());
-        PD_HIP(hipMemsetAsync(out, 0xFF, sizeof(int32_t) * m, s));   // -1
-    } else if (ix.metric == 0) {
-        query_m<T, 0>(ix, Q, m, out, bad, s);
-    } else {
-        query_m<T, 1>(ix, Q, m, out, bad, s);
-    }
-    unsigned long long nbad = 0;
-    read_u64(w, bad, 1, &nbad, s);
-    if (nbad) throw Error(-1, "pd_index_query: a query has a NaN or infinite coordinate");
-}
+// The predicate's bound on the accumulator at the index's eps.
+double threshold(const Index& ix) { return ix.metric == 0 ? ix.eps * ix.eps : ix.eps; }
 
 void check_bounds_ix(hipStream_t s, const char* kernel) {
 #if PD_CHECK_BOUNDS
@@ -1531,207 +1482,152 @@ void check_bounds_ix(hipStream_t s, const char* kernel) {
 #endif
 }
 
-// The list tier of a run-time k (DESIGN.md §12 has the resource report behind
-// it): registers up to 8, LDS above, with the block sized so that the list of
-// a block stays at 32 KiB — 256 lanes up to k = 16, 128 up to 32, 64 up to 64.
-template <typename T, int D, int M, typename K, int KT>
-void kdist_launch(Index& ix, const T* Q, uint64_t m, const uint32_t* order, int k, int lanes,
-                  double thr, double* out, unsigned long long* bad, hipStream_t s) {
-    const size_t lds = KT > 0 ? 0 : (size_t)k * lanes * sizeof(double);
-    hipLaunchKernelGGL((kdist_kernel<T, D, M, K, KT>), dim3((unsigned)((m + lanes - 1) / lanes)),
-                       dim3(lanes), lds, s, Q, m, order, ix.g, (const T*)ix.Xs, ix.nc,
-                       (const K*)ix.ckey, ix.cstart, ix.tab, ix.ntab, ix.ncells, ix.shift, thr, k,
-                       out, bad);
-    PD_HIP(hipGetLastError());
-    check_bounds_ix(s, "kdist_kernel");
-}
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <typename X>
+struct Tag {
+    using type = X;
+};
 
-template <typename T, int D, int M, typename K>
-void kdist_grid(Index& ix, const T* Q, uint64_t m, int k, double thr, double* out,
-                unsigned long long* bad, hipStream_t s) {
-    const uint32_t* order = query_order<T, D, K>(ix, Q, m, s);
-    if (k <= 4)
-        kdist_launch<T, D, M, K, 4>(ix, Q, m, order, k, kBlock, thr, out, bad, s);
-    else if (k <= 8)
-        kdist_launch<T, D, M, K, 8>(ix, Q, m, order, k, kBlock, thr, out, bad, s);
-    else
-        kdist_launch<T, D, M, K, 0>(ix, Q, m, order, k, k <= 16 ? 256 : k <= 32 ? 128 : 64, thr,
-                                    out, bad, s);
-}
-
-template <typename T, int D, int M>
-void kdist_grid_k(Index& ix, const T* Q, uint64_t m, int k, double thr, double* out,
-                  unsigned long long* bad, hipStream_t s) {
-    if (ix.key_bytes == 4)
-        kdist_grid<T, D, M, uint32_t>(ix, Q, m, k, thr, out, bad, s);
-    else
-        kdist_grid<T, D, M, uint64_t>(ix, Q, m, k, thr, out, bad, s);
-}
-
-template <typename T, int M>
-void kdist_dense(Index& ix, const T* Q, uint64_t m, int k, double thr, double* out,
-                 unsigned long long* bad, hipStream_t s) {
-    // LDS per lane: its query row and its k-slot list; per block also TC rows.
-    // The row limit is pd_index_query's (64 lanes of rows + one tile row in
-    // 60 KiB).  The block shrinks until its lanes' share is <= 48 KiB (never
-    // below 64 lanes); what then passes 60 KiB in all (long rows with a large
-    // k) asks for up to 144 KiB of the CU's 160 through the function attribute.
-    const size_t row = (size_t)ix.d * sizeof(T);
-    if ((size_t)64 * row + row + 4 > (60u << 10))
-        throw Error(-5, "pd_index_kdist: d too large for the tile kernel's LDS (d * itemsize <= 944)");
-    const size_t lane = row + (size_t)k * sizeof(double);
-    int QB = 256;
-    while (QB > 64 && (size_t)QB * lane > (48u << 10)) QB >>= 1;
-    const size_t budget = (size_t)QB * lane + row <= (60u << 10) ? (60u << 10) : (144u << 10);
-    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * lane) / row);
-    const size_t lds = (size_t)QB * lane + (size_t)TC * row;
+// One launch of a query kernel: a lane per query, `lanes` per block; the
+// arguments are the kernel's own parameter types.  Dynamic LDS beyond 64 KiB
+// (the tile kernels' large plans) needs the function attribute.
+template <typename... P>
+void launch(void (*kernel)(P...), const char* name, uint64_t m, int lanes, size_t lds,
+            hipStream_t s, typename Tag<P>::type... args) {
     if (lds > (64u << 10))
-        PD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_kdist_kernel<T, M>),
+        PD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((dense_kdist_kernel<T, M>), dim3((unsigned)((m + QB - 1) / QB)), dim3(QB),
-                       lds, s, Q, m, ix.d, (const T*)ix.Xs, ix.nc, TC, thr, k, out, bad);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((m + lanes - 1) / lanes)), dim3(lanes), lds, s,
+                       args...);
     PD_HIP(hipGetLastError());
-    check_bounds_ix(s, "dense_kdist_kernel");
+    check_bounds_ix(s, name);
 }
 
-template <typename T, int M>
-void kdist_m(Index& ix, const T* Q, uint64_t m, int k, double* out, unsigned long long* bad,
-             hipStream_t s) {
-    const double thr = M == 0 ? ix.eps * ix.eps : ix.eps;
-    switch (ix.d) {
-        case 1: kdist_grid_k<T, 1, M>(ix, Q, m, k, thr, out, bad, s); break;
-        case 2: kdist_grid_k<T, 2, M>(ix, Q, m, k, thr, out, bad, s); break;
-        case 3: kdist_grid_k<T, 3, M>(ix, Q, m, k, thr, out, bad, s); break;
-        case 4: kdist_grid_k<T, 4, M>(ix, Q, m, k, thr, out, bad, s); break;
-        default: kdist_dense<T, M>(ix, Q, m, k, thr, out, bad, s); break;
-    }
+// From the index's run-time dtype, metric, d and key width to compile-time
+// ones, as tags (std::integral_constant values, Tag<type>):
+//   d <= 4: grid(Tag<T>, Int<D>, Int<M>, Tag<K>)     d > 4: tile(Tag<T>, Int<M>)
+template <typename G, typename F>
+void dispatch(const Index& ix, G&& grid, F&& tile) {
+    auto by_d = [&](auto T, auto M) {
+        auto by_key = [&](auto D) {
+            if (ix.key_bytes == 4)
+                grid(T, D, M, Tag<uint32_t>{});
+            else
+                grid(T, D, M, Tag<uint64_t>{});
+        };
+        switch (ix.d) {
+            case 1: by_key(Int<1>{}); break;
+            case 2: by_key(Int<2>{}); break;
+            case 3: by_key(Int<3>{}); break;
+            case 4: by_key(Int<4>{}); break;
+            default: tile(T, M); break;
+        }
+    };
+    auto by_metric = [&](auto T) {
+        if (ix.metric == 0)
+            by_d(T, Int<0>{});
+        else
+            by_d(T, Int<1>{});
+    };
+    if (ix.dtype == 0)
+        by_metric(Tag<float>{});
+    else
+        by_metric(Tag<double>{});
 }
 
-template <typename T>
-void kdist_t(Index& ix, const T* Q, uint64_t m, int k, double* out, hipStream_t s) {
-    Ctx& w = ix.work;
-    unsigned long long* bad = w.arena.get<unsigned long long>("q_bad", 1);
-    PD_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
-    if (ix.nc < (uint64_t)k) {   // fewer than k rows in all (also: an empty index)
-        hipLaunchKernelGGL((finite_kernel<T>), dim3(grid_for((int64_t)(m * ix.d), 1024)),
-                           dim3(kBlock), 0, s, Q, m * (uint64_t)ix.d, bad);
-        PD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(fill_f64_kernel, dim3(blocks(m)), dim3(kBlock), 0, s, out, m,
-                           (double)INFINITY);
-        PD_HIP(hipGetLastError());
-    } else if (ix.metric == 0) {
-        kdist_m<T, 0>(ix, Q, m, k, out, bad, s);
-    } else {
-        kdist_m<T, 1>(ix, Q, m, k, out, bad, s);
-    }
-    unsigned long long nbad = 0;
-    read_u64(w, bad, 1, &nbad, s);
-    if (nbad) throw Error(-1, "pd_index_kdist: a query has a NaN or infinite coordinate");
-}
-
-// kdist_launch's tiers at 12 bytes per slot (DESIGN.md §14 has the resource
-// report): registers up to 8; LDS above with kdist's block sizes, so a block's
-// list is at most 48 KiB (256 lanes x 16, 128 x 32, 64 x 64 slots) and three
-// blocks share a CU's 160 KiB: 12, 6 and 3 waves per CU at the top of each tier.
-template <typename T, int D, int M, typename K, int KT>
-void knn_launch(Index& ix, const T* Q, uint64_t m, const uint32_t* order, int k, int lanes,
-                double thr, int32_t* ids, double* acc, unsigned long long* bad, hipStream_t s) {
-    // the LDS list: k pairs per lane and, for the write-out, the lane's query number
-    const size_t lds =
-        KT > 0 ? 0 : (size_t)lanes * (k * (sizeof(double) + sizeof(int32_t)) + sizeof(uint32_t));
-    hipLaunchKernelGGL((knn_kernel<T, D, M, K, KT>), dim3((unsigned)((m + lanes - 1) / lanes)),
-                       dim3(lanes), lds, s, Q, m, order, ix.g, (const T*)ix.Xs, ix.lab, ix.nc,
-                       (const K*)ix.ckey, ix.cstart, ix.tab, ix.ntab, ix.ncells, ix.shift, thr, k,
-                       ids, acc, bad);
-    PD_HIP(hipGetLastError());
-    check_bounds_ix(s, "knn_kernel");
-}
-
-template <typename T, int D, int M, typename K>
-void knn_grid(Index& ix, const T* Q, uint64_t m, int k, double thr, int32_t* ids, double* acc,
-              unsigned long long* bad, hipStream_t s) {
-    const uint32_t* order = query_order<T, D, K>(ix, Q, m, s);
+// The list tier of a run-time k, f(Int<KT>, lanes per block) (DESIGN.md §12 and
+// §14 have the resource reports behind it): registers up to 8 (KT slots), LDS
+// above (KT = 0) with the block sized so that a block's list of doubles stays at
+// 32 KiB — 256 lanes up to k = 16, 128 up to 32, 64 up to 64.  With 12 bytes per
+// slot (pairs) that is at most 48 KiB and three blocks share a CU's 160 KiB: 12,
+// 6 and 3 waves per CU at the top of each tier.
+template <typename F>
+void for_k_tier(int k, F&& f) {
     if (k <= 4)
-        knn_launch<T, D, M, K, 4>(ix, Q, m, order, k, kBlock, thr, ids, acc, bad, s);
+        f(Int<4>{}, kBlock);
     else if (k <= 8)
-        knn_launch<T, D, M, K, 8>(ix, Q, m, order, k, kBlock, thr, ids, acc, bad, s);
+        f(Int<8>{}, kBlock);
     else
-        knn_launch<T, D, M, K, 0>(ix, Q, m, order, k, k <= 16 ? 256 : k <= 32 ? 128 : 64, thr,
-                                  ids, acc, bad, s);
+        f(Int<0>{}, k <= 16 ? 256 : k <= 32 ? 128 : 64);
 }
 
-template <typename T, int D, int M>
-void knn_grid_k(Index& ix, const T* Q, uint64_t m, int k, double thr, int32_t* ids, double* acc,
-                unsigned long long* bad, hipStream_t s) {
-    if (ix.key_bytes == 4)
-        knn_grid<T, D, M, uint32_t>(ix, Q, m, k, thr, ids, acc, bad, s);
-    else
-        knn_grid<T, D, M, uint64_t>(ix, Q, m, k, thr, ids, acc, bad, s);
-}
-
-template <typename T, int M>
-void knn_dense(Index& ix, const T* Q, uint64_t m, int k, double thr, int32_t* ids, double* acc,
-               unsigned long long* bad, hipStream_t s) {
-    // kdist_dense's plan with 12 bytes per slot and a label per tile row.  Per
-    // lane: its query row and its k pairs; per block also TC rows and labels.
-    // The block shrinks until its lanes' share is <= 48 KiB (never below 64
-    // lanes); what then passes 60 KiB in all asks for up to 144 KiB through the
-    // function attribute (at most 64 * (944 + 768) = 107 KiB of lanes, which
-    // leaves 39 tile rows of 948 bytes).
-    const size_t row = (size_t)ix.d * sizeof(T);
+// The LDS plan of a tile kernel: QB lanes per block, TC rows per tile.  A lane
+// holds its query row and `lane_extra` bytes (its list), a tile row the row and
+// `tile_extra` bytes (its label).  The row limit is that 64 lanes of rows and
+// one labelled tile row fit 60 KiB.  The block shrinks until its lanes' share is
+// <= `lane_share` (never below 64 lanes); the tile takes what is left of 60 KiB,
+// or, where `large` allows it and not even one tile row fits, of 144 KiB of the
+// CU's 160 (through the function attribute: see launch).
+struct TilePlan {
+    int QB, TC;
+    size_t lds;
+};
+TilePlan plan_tiles(const Index& ix, size_t lane_extra, size_t tile_extra, size_t lane_share,
+                    bool large, const char* who) {
+    const size_t row = (size_t)ix.d * (ix.dtype == 0 ? sizeof(float) : sizeof(double));
     if ((size_t)64 * row + row + 4 > (60u << 10))
-        throw Error(-5, "pd_index_kneighbors: d too large for the tile kernel's LDS (d * itemsize <= 944)");
-    const size_t lane = row + (size_t)k * (sizeof(double) + sizeof(int32_t));
+        throw Error(-5, std::string(who) +
+                            ": d too large for the tile kernel's LDS (d * itemsize <= 944)");
+    const size_t lane = row + lane_extra, tile = row + tile_extra;
     int QB = 256;
-    while (QB > 64 && (size_t)QB * lane > (48u << 10)) QB >>= 1;
-    const size_t budget = (size_t)QB * lane + row + 4 <= (60u << 10) ? (60u << 10) : (144u << 10);
-    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * lane) / (row + 4));
-    const size_t lds = (size_t)QB * lane + (size_t)TC * (row + 4);
-    if (lds > (64u << 10))
-        PD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_knn_kernel<T, M>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((dense_knn_kernel<T, M>), dim3((unsigned)((m + QB - 1) / QB)), dim3(QB),
-                       lds, s, Q, m, ix.d, (const T*)ix.Xs, ix.lab, ix.nc, TC, thr, k, ids, acc,
-                       bad);
-    PD_HIP(hipGetLastError());
-    check_bounds_ix(s, "dense_knn_kernel");
+    while (QB > 64 && (size_t)QB * lane > lane_share) QB >>= 1;
+    const size_t budget =
+        !large || (size_t)QB * lane + tile <= (60u << 10) ? (60u << 10) : (144u << 10);
+    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * lane) / tile);
+    return {QB, TC, (size_t)QB * lane + (size_t)TC * tile};
 }
 
-template <typename T, int M>
-void knn_m(Index& ix, const T* Q, uint64_t m, int k, int32_t* ids, double* acc,
-           unsigned long long* bad, hipStream_t s) {
-    const double thr = M == 0 ? ix.eps * ix.eps : ix.eps;
-    switch (ix.d) {
-        case 1: knn_grid_k<T, 1, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
-        case 2: knn_grid_k<T, 2, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
-        case 3: knn_grid_k<T, 3, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
-        case 4: knn_grid_k<T, 4, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
-        default: knn_dense<T, M>(ix, Q, m, k, thr, ids, acc, bad, s); break;
-    }
+// The argument checks every query entry point shares (k: only where there is one).
+void check_args(const Index& ix, int dtype, int64_t m, const char* who, const int* k = nullptr) {
+    const std::string w(who);
+    if (k && *k < 1) throw Error(-1, w + ": k must be >= 1");
+    if (k && *k > kKdistMaxK) throw Error(-5, w + ": k must be <= PD_KDIST_MAX_K (64)");
+    if (dtype != ix.dtype) throw Error(-1, w + ": the queries' dtype differs from the index's");
+    if (m >= 0xFFFFFFFFll) throw Error(-5, w + ": m must be < 2^32 - 1");
 }
 
-// No short cut for an index with fewer than k rows: the walk returns the rows
-// there are.  An index without rows has nothing to walk.
-template <typename T>
-void knn_t(Index& ix, const T* Q, uint64_t m, int k, int32_t* ids, double* acc, hipStream_t s) {
+double radius_threshold(const Index& ix, int dtype, int64_t m, double radius, const char* who) {
+    const std::string w(who);
+    if (!(radius > 0) || !std::isfinite(radius))
+        throw Error(-1, w + ": radius must be a finite value > 0");
+    if (radius > ix.eps)
+        throw Error(-1, w + ": radius exceeds the eps the index was built with (its cells cover "
+                        "only eps)");
+    check_args(ix, dtype, m, who);
+    return ix.metric == 0 ? radius * radius : radius;
+}
+
+// The frame of a query call.  tally[0] counts the queries' non-finite
+// coordinates — by a sweep of its own when there is nothing to walk (`empty`:
+// on_empty(tally) then writes the results), by the kernels of body(tally)
+// otherwise —, and the call throws if there is one.  Returns tally[1], which is
+// the body's to use (both words come back in one round trip).
+template <typename E, typename B>
+unsigned long long run_checked(Index& ix, const void* Q, uint64_t m, bool empty, const char* who,
+                               hipStream_t s, E&& on_empty, B&& body) {
     Ctx& w = ix.work;
-    unsigned long long* bad = w.arena.get<unsigned long long>("q_bad", 1);
-    PD_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
-    if (ix.nc == 0) {
-        hipLaunchKernelGGL((finite_kernel<T>), dim3(grid_for((int64_t)(m * ix.d), 1024)),
-                           dim3(kBlock), 0, s, Q, m * (uint64_t)ix.d, bad);
+    unsigned long long* tally = w.arena.get<unsigned long long>("q_bad", 2);
+    PD_HIP(hipMemsetAsync(tally, 0, 2 * sizeof(unsigned long long), s));
+    if (empty) {
+        const uint64_t total = m * (uint64_t)ix.d;
+        const dim3 grid(grid_for((int64_t)total, 1024));
+        if (ix.dtype == 0)
+            hipLaunchKernelGGL((finite_kernel<float>), grid, dim3(kBlock), 0, s, (const float*)Q,
+                               total, tally);
+        else
+            hipLaunchKernelGGL((finite_kernel<double>), grid, dim3(kBlock), 0, s, (const double*)Q,
+                               total, tally);
         PD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(knn_empty_kernel, dim3(blocks(m * (uint64_t)k)), dim3(kBlock), 0, s,
-                           ids, acc, m * (uint64_t)k);
-        PD_HIP(hipGetLastError());
-    } else if (ix.metric == 0) {
-        knn_m<T, 0>(ix, Q, m, k, ids, acc, bad, s);
+        on_empty(tally);
     } else {
-        knn_m<T, 1>(ix, Q, m, k, ids, acc, bad, s);
+        body(tally);
     }
-    unsigned long long nbad = 0;
-    read_u64(w, bad, 1, &nbad, s);
-    if (nbad) throw Error(-1, "pd_index_kneighbors: a query has a NaN or infinite coordinate");
+    unsigned long long* h = (unsigned long long*)pinned(w, 2 * sizeof(unsigned long long));
+    PD_HIP(hipMemcpyAsync(h, tally, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    sync(s);
+    if (h[0]) throw Error(-1, std::string(who) + ": a query has a NaN or infinite coordinate");
+    return h[1];
 }
 
 // One pass of a radius query: the count (cnt) or a fill (off, ids, acc, cap).
@@ -1745,94 +1641,36 @@ struct RadiusCall {
     unsigned long long* tally;   // [0] non-finite queries, [1] segments that do not fit their hits
 };
 
-template <typename T, int D, int M, typename K, int FILL>
-void radius_grid(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
-    const uint32_t* order = query_order<T, D, K>(ix, Q, m, s);
-    hipLaunchKernelGGL((radius_kernel<T, D, M, K, FILL>), dim3(blocks(m)), dim3(kBlock), 0, s, Q, m,
-                       order, ix.g, (const T*)ix.Xs, ix.lab, ix.nc, (const K*)ix.ckey, ix.cstart,
-                       ix.tab, ix.ntab, ix.ncells, ix.shift, rc.thr, rc.cnt, rc.off, rc.ids, rc.acc,
-                       rc.cap, rc.tally);
-    PD_HIP(hipGetLastError());
-    check_bounds_ix(s, "radius_kernel");
-}
-
-template <typename T, int D, int M, int FILL>
-void radius_grid_k(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
-    if (ix.key_bytes == 4)
-        radius_grid<T, D, M, uint32_t, FILL>(ix, Q, m, rc, s);
+// Either pass over a non-empty index.  FILL: 0 the count, 1 labels, 2 labels
+// and accumulators.
+void radius_pass(Index& ix, const void* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
+    auto pass = [&](auto F) {
+        constexpr int FILL = decltype(F)::value;
+        dispatch(
+            ix,
+            [&](auto T, auto D, auto M, auto K) {
+                using Tq = typename decltype(T)::type;
+                using Kq = typename decltype(K)::type;
+                constexpr int Dv = decltype(D)::value, Mv = decltype(M)::value;
+                const uint32_t* order = query_order<Tq, Dv, Kq>(ix, (const Tq*)Q, m, s);
+                launch(radius_kernel<Tq, Dv, Mv, Kq, FILL>, "radius_kernel", m, kBlock, 0, s,
+                       (const Tq*)Q, m, order, view_of<Tq, Kq>(ix), rc.thr, rc.cnt, rc.off, rc.ids,
+                       rc.acc, rc.cap, rc.tally);
+            },
+            [&](auto T, auto M) {
+                using Tq = typename decltype(T)::type;
+                const TilePlan p = plan_tiles(ix, 0, 4, 32u << 10, false, "pd_index_radius");
+                launch(dense_radius_kernel<Tq, decltype(M)::value, FILL>, "dense_radius_kernel", m,
+                       p.QB, p.lds, s, (const Tq*)Q, m, ix.d, (const Tq*)ix.Xs, ix.lab, ix.nc, p.TC,
+                       rc.thr, rc.cnt, rc.off, rc.ids, rc.acc, rc.cap, rc.tally);
+            });
+    };
+    if (!rc.off)
+        pass(Int<0>{});
+    else if (!rc.acc)
+        pass(Int<1>{});
     else
-        radius_grid<T, D, M, uint64_t, FILL>(ix, Q, m, rc, s);
-}
-
-template <typename T, int M, int FILL>
-void radius_dense(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
-    // pd_index_query's LDS plan: QB query rows + TC rows and labels in 60 KiB
-    const size_t row = (size_t)ix.d * sizeof(T);
-    int QB = 256;
-    while (QB > 64 && (size_t)QB * row > (32u << 10)) QB >>= 1;
-    const size_t budget = 60u << 10;
-    if ((size_t)QB * row + row + 4 > budget)
-        throw Error(-5, "pd_index_radius: d too large for the tile kernel's LDS (d * itemsize <= 944)");
-    const int TC = (int)std::min<size_t>(64, (budget - (size_t)QB * row) / (row + 4));
-    const size_t lds = (size_t)QB * row + (size_t)TC * (row + 4);
-    hipLaunchKernelGGL((dense_radius_kernel<T, M, FILL>), dim3((unsigned)((m + QB - 1) / QB)),
-                       dim3(QB), lds, s, Q, m, ix.d, (const T*)ix.Xs, ix.lab, ix.nc, TC, rc.thr,
-                       rc.cnt, rc.off, rc.ids, rc.acc, rc.cap, rc.tally);
-    PD_HIP(hipGetLastError());
-    check_bounds_ix(s, "dense_radius_kernel");
-}
-
-template <typename T, int M, int FILL>
-void radius_m(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
-    switch (ix.d) {
-        case 1: radius_grid_k<T, 1, M, FILL>(ix, Q, m, rc, s); break;
-        case 2: radius_grid_k<T, 2, M, FILL>(ix, Q, m, rc, s); break;
-        case 3: radius_grid_k<T, 3, M, FILL>(ix, Q, m, rc, s); break;
-        case 4: radius_grid_k<T, 4, M, FILL>(ix, Q, m, rc, s); break;
-        default: radius_dense<T, M, FILL>(ix, Q, m, rc, s); break;
-    }
-}
-
-template <typename T, int FILL>
-void radius_f(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
-    if (ix.metric == 0)
-        radius_m<T, 0, FILL>(ix, Q, m, rc, s);
-    else
-        radius_m<T, 1, FILL>(ix, Q, m, rc, s);
-}
-
-// Either pass over a non-empty index; an empty one only checks the queries
-// (and, for a fill, that every segment is empty).
-template <typename T>
-void radius_t(Index& ix, const T* Q, uint64_t m, const RadiusCall& rc, hipStream_t s) {
-    if (ix.nc == 0) {
-        hipLaunchKernelGGL((finite_kernel<T>), dim3(grid_for((int64_t)(m * ix.d), 1024)),
-                           dim3(kBlock), 0, s, Q, m * (uint64_t)ix.d, rc.tally);
-        PD_HIP(hipGetLastError());
-        if (rc.off) {
-            hipLaunchKernelGGL(radius_empty_kernel, dim3(blocks(m)), dim3(kBlock), 0, s, rc.off, m,
-                               rc.cap, rc.tally);
-            PD_HIP(hipGetLastError());
-        }
-    } else if (!rc.off) {
-        radius_f<T, 0>(ix, Q, m, rc, s);
-    } else if (!rc.acc) {
-        radius_f<T, 1>(ix, Q, m, rc, s);
-    } else {
-        radius_f<T, 2>(ix, Q, m, rc, s);
-    }
-}
-
-double radius_threshold(const Index& ix, int dtype, int64_t m, double radius, const char* who) {
-    const std::string w(who);
-    if (!(radius > 0) || !std::isfinite(radius))
-        throw Error(-1, w + ": radius must be a finite value > 0");
-    if (radius > ix.eps)
-        throw Error(-1, w + ": radius exceeds the eps the index was built with (its cells cover "
-                        "only eps)");
-    if (dtype != ix.dtype) throw Error(-1, w + ": the queries' dtype differs from the index's");
-    if (m >= 0xFFFFFFFFll) throw Error(-5, w + ": m must be < 2^32 - 1");
-    return ix.metric == 0 ? radius * radius : radius;
+        pass(Int<2>{});
 }
 
 }  // namespace
@@ -1872,42 +1710,125 @@ Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const
 }
 
 void index_query(Index* ix, const void* Q, int dtype, int64_t m, int32_t* out, hipStream_t s) {
-    if (dtype != ix->dtype) throw Error(-1, "pd_index_query: the queries' dtype differs from the index's");
-    if (m >= 0xFFFFFFFFll) throw Error(-5, "pd_index_query: m must be < 2^32 - 1");
+    check_args(*ix, dtype, m, "pd_index_query");
     if (m == 0) return;
-    if (ix->dtype == 0)
-        query_t<float>(*ix, (const float*)Q, (uint64_t)m, out, s);
-    else
-        query_t<double>(*ix, (const double*)Q, (uint64_t)m, out, s);
+    const uint64_t um = (uint64_t)m;
+    run_checked(
+        *ix, Q, um, ix->nc == 0, "pd_index_query", s,
+        [&](unsigned long long*) {
+            PD_HIP(hipMemsetAsync(out, 0xFF, sizeof(int32_t) * um, s));   // -1
+        },
+        [&](unsigned long long* bad) {
+            dispatch(
+                *ix,
+                [&](auto T, auto D, auto M, auto K) {
+                    using Tq = typename decltype(T)::type;
+                    using Kq = typename decltype(K)::type;
+                    constexpr int Dv = decltype(D)::value, Mv = decltype(M)::value;
+                    const uint32_t* order = query_order<Tq, Dv, Kq>(*ix, (const Tq*)Q, um, s);
+                    launch(query_kernel<Tq, Dv, Mv, Kq>, "query_kernel", um, kBlock, 0, s,
+                           (const Tq*)Q, um, order, view_of<Tq, Kq>(*ix), ix->eps,
+                           ix->eps * ix->eps, ix->slo, ix->shi, out, bad);
+                },
+                [&](auto T, auto M) {
+                    using Tq = typename decltype(T)::type;
+                    const TilePlan p = plan_tiles(*ix, 0, 4, 32u << 10, false, "pd_index_query");
+                    launch(dense_query_kernel<Tq, decltype(M)::value>, "dense_query_kernel", um,
+                           p.QB, p.lds, s, (const Tq*)Q, um, ix->d, (const Tq*)ix->Xs, ix->lab,
+                           ix->nc, p.TC, threshold(*ix), out, bad);
+                });
+        });
 }
 
 void index_kdist(Index* ix, const void* Q, int dtype, int64_t m, int k, double* out,
                  hipStream_t s) {
-    if (k < 1) throw Error(-1, "pd_index_kdist: k must be >= 1");
-    if (k > kKdistMaxK) throw Error(-5, "pd_index_kdist: k must be <= PD_KDIST_MAX_K (64)");
-    if (dtype != ix->dtype) throw Error(-1, "pd_index_kdist: the queries' dtype differs from the index's");
-    if (m >= 0xFFFFFFFFll) throw Error(-5, "pd_index_kdist: m must be < 2^32 - 1");
+    check_args(*ix, dtype, m, "pd_index_kdist", &k);
     if (m == 0) return;
-    if (ix->dtype == 0)
-        kdist_t<float>(*ix, (const float*)Q, (uint64_t)m, k, out, s);
-    else
-        kdist_t<double>(*ix, (const double*)Q, (uint64_t)m, k, out, s);
+    const uint64_t um = (uint64_t)m;
+    const double thr = threshold(*ix);
+    run_checked(
+        *ix, Q, um, ix->nc < (uint64_t)k,   // fewer than k rows in all (also: an empty index)
+        "pd_index_kdist", s,
+        [&](unsigned long long*) {
+            hipLaunchKernelGGL(fill_f64_kernel, dim3(blocks(um)), dim3(kBlock), 0, s, out, um,
+                               (double)INFINITY);
+            PD_HIP(hipGetLastError());
+        },
+        [&](unsigned long long* bad) {
+            dispatch(
+                *ix,
+                [&](auto T, auto D, auto M, auto K) {
+                    using Tq = typename decltype(T)::type;
+                    using Kq = typename decltype(K)::type;
+                    constexpr int Dv = decltype(D)::value, Mv = decltype(M)::value;
+                    const uint32_t* order = query_order<Tq, Dv, Kq>(*ix, (const Tq*)Q, um, s);
+                    for_k_tier(k, [&](auto KT, int lanes) {
+                        constexpr int KTv = decltype(KT)::value;
+                        const size_t lds = KTv > 0 ? 0 : (size_t)k * lanes * sizeof(double);
+                        launch(kdist_kernel<Tq, Dv, Mv, Kq, KTv>, "kdist_kernel", um, lanes, lds, s,
+                               (const Tq*)Q, um, order, view_of<Tq, Kq>(*ix), thr, k, out, bad);
+                    });
+                },
+                [&](auto T, auto M) {
+                    using Tq = typename decltype(T)::type;
+                    const TilePlan p = plan_tiles(*ix, (size_t)k * sizeof(double), 0, 48u << 10,
+                                                  true, "pd_index_kdist");
+                    launch(dense_kdist_kernel<Tq, decltype(M)::value>, "dense_kdist_kernel", um,
+                           p.QB, p.lds, s, (const Tq*)Q, um, ix->d, (const Tq*)ix->Xs, ix->nc, p.TC,
+                           thr, k, out, bad);
+                });
+        });
 }
 
+// No short cut for an index with fewer than k rows: the walk returns the rows
+// there are.  An index without rows has nothing to walk.
 void index_kneighbors(Index* ix, const void* Q, int dtype, int64_t m, int k, int32_t* ids,
                       double* acc, hipStream_t s) {
-    if (k < 1) throw Error(-1, "pd_index_kneighbors: k must be >= 1");
-    if (k > kKdistMaxK) throw Error(-5, "pd_index_kneighbors: k must be <= PD_KDIST_MAX_K (64)");
-    if (dtype != ix->dtype)
-        throw Error(-1, "pd_index_kneighbors: the queries' dtype differs from the index's");
-    if (m >= 0xFFFFFFFFll) throw Error(-5, "pd_index_kneighbors: m must be < 2^32 - 1");
+    check_args(*ix, dtype, m, "pd_index_kneighbors", &k);
     if (m == 0) return;
-    if (ix->dtype == 0)
-        knn_t<float>(*ix, (const float*)Q, (uint64_t)m, k, ids, acc, s);
-    else
-        knn_t<double>(*ix, (const double*)Q, (uint64_t)m, k, ids, acc, s);
+    const uint64_t um = (uint64_t)m;
+    const double thr = threshold(*ix);
+    constexpr size_t kSlot = sizeof(double) + sizeof(int32_t);   // a pair
+    run_checked(
+        *ix, Q, um, ix->nc == 0, "pd_index_kneighbors", s,
+        [&](unsigned long long*) {
+            hipLaunchKernelGGL(knn_empty_kernel, dim3(blocks(um * (uint64_t)k)), dim3(kBlock), 0, s,
+                               ids, acc, um * (uint64_t)k);
+            PD_HIP(hipGetLastError());
+        },
+        [&](unsigned long long* bad) {
+            dispatch(
+                *ix,
+                [&](auto T, auto D, auto M, auto K) {
+                    using Tq = typename decltype(T)::type;
+                    using Kq = typename decltype(K)::type;
+                    constexpr int Dv = decltype(D)::value, Mv = decltype(M)::value;
+                    const uint32_t* order = query_order<Tq, Dv, Kq>(*ix, (const Tq*)Q, um, s);
+                    for_k_tier(k, [&](auto KT, int lanes) {
+                        constexpr int KTv = decltype(KT)::value;
+                        // the LDS list: k pairs per lane and, for the write-out, the
+                        // lane's query number
+                        const size_t lds =
+                            KTv > 0 ? 0 : (size_t)lanes * (k * kSlot + sizeof(uint32_t));
+                        launch(knn_kernel<Tq, Dv, Mv, Kq, KTv>, "knn_kernel", um, lanes, lds, s,
+                               (const Tq*)Q, um, order, view_of<Tq, Kq>(*ix), thr, k, ids, acc, bad);
+                    });
+                },
+                [&](auto T, auto M) {
+                    using Tq = typename decltype(T)::type;
+                    // at most 64 * (944 + 768) = 107 KiB of lanes, which leaves 39
+                    // tile rows of 948 bytes
+                    const TilePlan p = plan_tiles(*ix, (size_t)k * kSlot, 4, 48u << 10, true,
+                                                  "pd_index_kneighbors");
+                    launch(dense_knn_kernel<Tq, decltype(M)::value>, "dense_knn_kernel", um, p.QB,
+                           p.lds, s, (const Tq*)Q, um, ix->d, (const Tq*)ix->Xs, ix->lab, ix->nc,
+                           p.TC, thr, k, ids, acc, bad);
+                });
+        });
 }
 
+// An empty index only checks the queries (and, for a fill, that every segment
+// is empty).
 void index_radius_count(Index* ix, const void* Q, int dtype, int64_t m, double radius,
                         int64_t* offsets, int64_t* total_host, hipStream_t s) {
     RadiusCall rc{};
@@ -1918,33 +1839,26 @@ void index_radius_count(Index* ix, const void* Q, int dtype, int64_t m, double r
     if (m == 0) return;
     Ctx& w = ix->work;
     const uint64_t um = (uint64_t)m;
-    rc.tally = w.arena.get<unsigned long long>("q_bad", 2);
-    PD_HIP(hipMemsetAsync(rc.tally, 0, 2 * sizeof(unsigned long long), s));
-    if (ix->nc) {
-        rc.cnt = w.arena.get<uint32_t>("r_cnt", um + 1);
-        PD_HIP(hipMemsetAsync(rc.cnt + um, 0, sizeof(uint32_t), s));
-    }
-    if (ix->dtype == 0)
-        radius_t<float>(*ix, (const float*)Q, um, rc, s);
-    else
-        radius_t<double>(*ix, (const double*)Q, um, rc, s);
-    if (ix->nc) {
-        // 32-bit counts, 64-bit sums: the total passes 2^32 long before n does
-        uint64_t* off = reinterpret_cast<uint64_t*>(offsets);
-        size_t tb = 0;
-        PD_HIP(rocprim::exclusive_scan(nullptr, tb, rc.cnt, off, (uint64_t)0, (size_t)um + 1,
-                                       rocprim::plus<uint64_t>(), s));
-        void* tmp = w.arena.get<char>("r_scan_tmp", tb);
-        PD_HIP(rocprim::exclusive_scan(tmp, tb, rc.cnt, off, (uint64_t)0, (size_t)um + 1,
-                                       rocprim::plus<uint64_t>(), s));
-    }
-    // the non-finite tally and the total in one round trip
-    unsigned long long* h = (unsigned long long*)pinned(w, 2 * sizeof(unsigned long long));
-    PD_HIP(hipMemcpyAsync(h, rc.tally, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    PD_HIP(hipMemcpyAsync(h + 1, offsets + um, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    sync(s);
-    if (h[0]) throw Error(-1, "pd_index_radius_count: a query has a NaN or infinite coordinate");
-    if (total_host) *total_host = (int64_t)h[1];
+    // the total rides the frame's round trip as tally[1] (0 for an empty index)
+    const unsigned long long total = run_checked(
+        *ix, Q, um, ix->nc == 0, "pd_index_radius_count", s, [](unsigned long long*) {},
+        [&](unsigned long long* tally) {
+            rc.tally = tally;
+            rc.cnt = w.arena.get<uint32_t>("r_cnt", um + 1);
+            PD_HIP(hipMemsetAsync(rc.cnt + um, 0, sizeof(uint32_t), s));
+            radius_pass(*ix, Q, um, rc, s);
+            // 32-bit counts, 64-bit sums: the total passes 2^32 long before n does
+            uint64_t* off = reinterpret_cast<uint64_t*>(offsets);
+            size_t tb = 0;
+            PD_HIP(rocprim::exclusive_scan(nullptr, tb, rc.cnt, off, (uint64_t)0, (size_t)um + 1,
+                                           rocprim::plus<uint64_t>(), s));
+            void* tmp = w.arena.get<char>("r_scan_tmp", tb);
+            PD_HIP(rocprim::exclusive_scan(tmp, tb, rc.cnt, off, (uint64_t)0, (size_t)um + 1,
+                                           rocprim::plus<uint64_t>(), s));
+            PD_HIP(hipMemcpyAsync(tally + 1, offsets + um, sizeof(int64_t),
+                                  hipMemcpyDeviceToDevice, s));
+        });
+    if (total_host) *total_host = (int64_t)total;
 }
 
 void index_radius_fill(Index* ix, const void* Q, int dtype, int64_t m, double radius,
@@ -1954,22 +1868,24 @@ void index_radius_fill(Index* ix, const void* Q, int dtype, int64_t m, double ra
     rc.thr = radius_threshold(*ix, dtype, m, radius, "pd_index_radius_fill");
     if (capacity < 0) throw Error(-1, "pd_index_radius_fill: capacity < 0");
     if (m == 0) return;
-    Ctx& w = ix->work;
+    const uint64_t um = (uint64_t)m;
     rc.off = offsets;
     rc.ids = ids;
     rc.acc = acc;
     rc.cap = capacity;
-    rc.tally = w.arena.get<unsigned long long>("q_bad", 2);
-    PD_HIP(hipMemsetAsync(rc.tally, 0, 2 * sizeof(unsigned long long), s));
-    if (ix->dtype == 0)
-        radius_t<float>(*ix, (const float*)Q, (uint64_t)m, rc, s);
-    else
-        radius_t<double>(*ix, (const double*)Q, (uint64_t)m, rc, s);
-    unsigned long long t[2] = {0, 0};
-    read_u64(w, rc.tally, 2, t, s);
-    if (t[0]) throw Error(-1, "pd_index_radius_fill: a query has a NaN or infinite coordinate");
-    if (t[1])
-        throw Error(-1, "pd_index_radius_fill: " + std::to_string(t[1]) + " queries' hits do not "
+    const unsigned long long misfits = run_checked(
+        *ix, Q, um, ix->nc == 0, "pd_index_radius_fill", s,
+        [&](unsigned long long* tally) {
+            hipLaunchKernelGGL(radius_empty_kernel, dim3(blocks(um)), dim3(kBlock), 0, s, offsets,
+                               um, capacity, tally);
+            PD_HIP(hipGetLastError());
+        },
+        [&](unsigned long long* tally) {
+            rc.tally = tally;
+            radius_pass(*ix, Q, um, rc, s);
+        });
+    if (misfits)
+        throw Error(-1, "pd_index_radius_fill: " + std::to_string(misfits) + " queries' hits do not "
                         "fit their segments: Q, radius or offsets changed since the count");
 }
 
