@@ -873,7 +873,25 @@ __global__ __launch_bounds__(kBlock) void dir_write_kernel(uint4* __restrict__ d
 // The count pass keeps the two smallest neighbours it saw (mn2[r]): the
 // parent is the smaller of them that is core and below r — two candidates
 // leave about half the trees of one (tools/init_forest_study.py).
-constexpr int kSubTiles = 4;   // init_kernel / roots_kernel: record tiles per block
+//
+// The count sweep leaves early in the centre row, so that parent usually lies
+// a few records back in key order: long chains of short hops, which every
+// later root walk (window_uf_kernel's lock-step rounds, the cell roots) pays
+// for in dependent loads.  A block owns kInitSub * kBlock consecutive records,
+// so it stages their parents in LDS and jumps pointers there until every
+// record points at its first ancestor outside the tile, or at the chain's root
+// when that lies inside: same trees, same roots, no further pass over memory.
+// A 1-D chain at min_samples = 3 is as long as the tile, hence jumping rounds
+// with a block vote (at most log2(tile) + 1 of them) and no per-lane walk.
+// C2 link 3.93 / 3.90 / 3.88 ms at tiles of 1024 / 2048 / 4096 records (16 KB
+// of LDS at 4096).  PD_INIT_SUB is an A/B override
+// (tools/build_variant.sh "-DPD_INIT_SUB=4").
+#ifndef PD_INIT_SUB
+#define PD_INIT_SUB 16
+#endif
+constexpr int kInitSub = PD_INIT_SUB;   // init_kernel: record tiles per block
+constexpr uint32_t kInitTile = (uint32_t)kInitSub * kBlock;
+static_assert(kInitSub >= 1 && kInitTile * 4 <= 65536, "a block's static LDS");
 #ifndef PD_ROOTS_SUB
 #define PD_ROOTS_SUB 4
 #endif
@@ -887,28 +905,82 @@ __global__ __launch_bounds__(kBlock) void init_kernel(uint32_t R, const uint8_t*
                                                       uint32_t* __restrict__ gmin,
                                                       uint32_t* __restrict__ wroot, uint64_t W,
                                                       uint32_t* __restrict__ kbits, uint64_t NW) {
-    // kSubTiles record tiles of kBlock per block (fewer workgroups for the
-    // light per-record passes over 1e9 records)
+    // kInitSub record tiles of kBlock per block (fewer workgroups for the
+    // light per-record passes over 1e9 records); slot e of the tile is
+    // record base + e, lane t owns the slots t + q * kBlock
+    __shared__ uint32_t lp[kInitTile];
+    const uint64_t base = (uint64_t)blockIdx.x * kInitTile;
+    uint32_t p[kInitSub];
 #pragma unroll
-    for (int q = 0; q < kSubTiles; ++q) {
-        const uint64_t r64 = ((uint64_t)blockIdx.x * kSubTiles + q) * kBlock + threadIdx.x;
+    for (int q = 0; q < kInitSub; ++q) {
+        const uint32_t e = (uint32_t)q * kBlock + threadIdx.x;
+        const uint64_t r64 = base + e;
         if (r64 < W) wroot[r64] = kNone;
         if (r64 < NW) kbits[r64] = 0u;   // the component-key bitmap (rank_roots)
-        if (r64 >= R) continue;
-        const uint32_t r = (uint32_t)r64;
-        gmin[r] = kNone;
-        uint32_t p = kNone;
-        if (core[r] & 1) {
-            p = r;
-            if (use_mn) {
-                const uint2 m = reinterpret_cast<const uint2*>(mn)[r];
-                if (m.x < r && (core[m.x] & 1))
-                    p = m.x;
-                else if (m.y < r && (core[m.y] & 1))
-                    p = m.y;
+        p[q] = kNone;
+        if (r64 < R) {
+            const uint32_t r = (uint32_t)r64;
+            gmin[r] = kNone;
+            if (core[r] & 1) {
+                p[q] = r;
+                if (use_mn) {
+                    const uint2 m = reinterpret_cast<const uint2*>(mn)[r];
+                    if (m.x < r && (core[m.x] & 1))
+                        p[q] = m.x;
+                    else if (m.y < r && (core[m.y] & 1))
+                        p[q] = m.y;
+                }
             }
         }
-        par[r] = p;
+        lp[e] = p[q];
+    }
+    if (base >= R) return;   // (the whole block: it only fills)
+    // Pointer jumping in LDS, in place.  A slot is open (bit q of `open`)
+    // while its parent lies in the tile and is not known to be a root; a
+    // round gives every open slot its parent's parent.  A slot is written by
+    // its owner only, and a reader that meets either the older or the newer
+    // value gets an ancestor (parents only decrease), so one barrier per
+    // round does: the vote.  A round at least doubles every open slot's hops,
+    // so there are at most log2(kInitTile) moving rounds and one that finds
+    // nothing to move.
+    const uint32_t b32 = (uint32_t)base;
+    uint32_t open = 0;
+#pragma unroll
+    for (int q = 0; q < kInitSub; ++q) {
+        const uint32_t e = (uint32_t)q * kBlock + threadIdx.x;
+        if (p[q] != kNone && p[q] != b32 + e && p[q] >= b32) open |= 1u << q;
+    }
+    __syncthreads();   // the staging
+    while (true) {
+        uint32_t g[kInitSub];
+#pragma unroll
+        for (int q = 0; q < kInitSub; ++q) {
+            g[q] = p[q];
+            if ((open >> q & 1u) && PD_OK(p[q] - b32 < kInitTile, 9, p[q]))
+                g[q] = __hip_atomic_load(lp + (p[q] - b32), __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        int moved = 0;
+#pragma unroll
+        for (int q = 0; q < kInitSub; ++q) {
+            if (!(open >> q & 1u)) continue;
+            // the parent is a root of the tile (kNone: never, a parent is core)
+            if (g[q] == p[q] || g[q] == kNone) {
+                open &= ~(1u << q);
+                continue;
+            }
+            p[q] = g[q];
+            __hip_atomic_store(lp + ((uint32_t)q * kBlock + threadIdx.x), g[q], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+            moved = 1;
+            if (g[q] < b32) open &= ~(1u << q);   // the first ancestor outside the tile
+        }
+        if (!__syncthreads_or(moved)) break;
+    }
+#pragma unroll
+    for (int q = 0; q < kInitSub; ++q) {
+        const uint64_t r64 = base + (uint32_t)q * kBlock + threadIdx.x;
+        if (r64 < R) par[r64] = p[q];
     }
 }
 
@@ -2598,8 +2670,8 @@ struct EvTimer {
 };
 
 inline unsigned blocks(uint64_t n) { return n ? (unsigned)((n + kBlock - 1) / kBlock) : 1u; }
-// blocks of `sub` record tiles (init_kernel: kSubTiles, roots_kernel: kRootSub)
-inline unsigned sub_blocks(uint64_t n, int sub = kSubTiles) {
+// blocks of `sub` record tiles (init_kernel: kInitSub, roots_kernel: kRootSub)
+inline unsigned sub_blocks(uint64_t n, int sub) {
     return n ? (unsigned)((n + (uint64_t)kBlock * sub - 1) / ((uint64_t)kBlock * sub)) : 1u;
 }
 
@@ -3042,8 +3114,10 @@ void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t
         const uint64_t NW = a.phase == 0 ? (n + 31) / 32 : 0;
         const uint64_t NWz = NW ? ((NW + 31) & ~uint64_t(31)) + kRootLists * kRootCntStride : 0;
         uint32_t* kbits = NW ? ctx.arena.get<uint32_t>("key_bits", NWz) : nullptr;
-        hipLaunchKernelGGL(init_kernel, dim3(sub_blocks(std::max<uint64_t>(std::max<uint64_t>(R, W), NWz))),
+        hipLaunchKernelGGL(init_kernel,
+                           dim3(sub_blocks(std::max<uint64_t>(std::max<uint64_t>(R, W), NWz), kInitSub)),
                            dim3(kBlock), 0, s, R, core, mn, 1, par, gmin, wroot, (uint64_t)W, kbits, NWz);
+        check_bounds(s, "init_kernel");
         // (2) window union.  Auto window (PD_OPT_CENTRE_WINDOW < 0): sparse
         // cells (a few records each, C2: 2.3) gain little from the window
         // beyond the fused flatten, so a short one is cheapest (C2 link 6.59
