@@ -2675,17 +2675,22 @@ inline unsigned sub_blocks(uint64_t n, int sub) {
     return n ? (unsigned)((n + (uint64_t)kBlock * sub - 1) / ((uint64_t)kBlock * sub)) : 1u;
 }
 
+// rocPRIM's exclusive prefix sum (in the type of `init`) on s, its temporary
+// storage from the arena buffer `tmp_name`.
+template <typename In, typename Out, typename V>
+void exclusive_sum(Ctx& ctx, const char* tmp_name, In in, Out out, V init, size_t n, hipStream_t s) {
+    size_t tb = 0;
+    PD_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, init, n, rocprim::plus<V>(), s));
+    void* tmp = ctx.arena.get<char>(tmp_name, tb);
+    PD_HIP(rocprim::exclusive_scan(tmp, tb, in, out, init, n, rocprim::plus<V>(), s));
+}
+
 // Exclusive scan of `tiles` per-tile counts into u64 offsets (off[tiles] =
 // total); with `read_total` the total is copied back (syncs) and returned.
 uint64_t tile_offsets(Ctx& ctx, uint32_t* cnt, unsigned tiles, uint64_t* off, hipStream_t s,
                       bool read_total) {
     // (cnt[tiles] = 0: written by the tile kernel's block 0, tile_count_out)
-    size_t tb = 0;
-    PD_HIP(rocprim::exclusive_scan(nullptr, tb, cnt, off, (uint64_t)0, (size_t)tiles + 1,
-                                   rocprim::plus<uint64_t>(), s));
-    void* tmp = ctx.arena.get<char>("tile_scan_tmp", tb);
-    PD_HIP(rocprim::exclusive_scan(tmp, tb, cnt, off, (uint64_t)0, (size_t)tiles + 1,
-                                   rocprim::plus<uint64_t>(), s));
+    exclusive_sum(ctx, "tile_scan_tmp", cnt, off, (uint64_t)0, (size_t)tiles + 1, s);
     if (!read_total) return 0;
     uint64_t* h = (uint64_t*)pinned(ctx, sizeof(uint64_t));
     PD_HIP(hipMemcpyAsync(h, off + tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -2694,19 +2699,15 @@ uint64_t tile_offsets(Ctx& ctx, uint32_t* cnt, unsigned tiles, uint64_t* off, hi
 }
 inline int xsub_of(const Ctx& ctx) { return ctx.xsub < 1 ? 1 : ctx.xsub; }
 
-// Launch helpers for the two neighbour sweeps.  The count sweep runs at 8
-// waves per SIMD (64 VGPRs); its instrumented form (PD_OPT_SWEEP_STATS)
-// without the register cap.
-template <typename T, int D, int M, bool ST>
-void launch_count(hipStream_t s, const T* Xs, uint32_t R, const Cells& C, double eps, double eps2,
-                  float lo, float hi, uint32_t ms, int full, uint32_t rot_min, uint8_t* core,
-                  uint32_t* mn, uint32_t* cnt, unsigned long long* st) {
-    if constexpr (ST)
-        hipLaunchKernelGGL((count4_kernel<T, D, M, true, 1>), dim3(blocks(R)), dim3(kBlock), 0, s,
-                           Xs, R, C, eps, eps2, lo, hi, ms, full, rot_min, core, mn, cnt, st, 0u);
-    else
-        hipLaunchKernelGGL((count4_kernel<T, D, M, false, kCountWpe>), dim3(blocks(R)), dim3(kBlock), 0, s,
-                           Xs, R, C, eps, eps2, lo, hi, ms, full, rot_min, core, mn, cnt, st, 0u);
+// The per-tile counts and their scanned offsets (tiles + 1 words each) that
+// every two-pass compaction shares: tile kernel, tile_offsets, write kernel.
+inline std::pair<uint32_t*, uint64_t*> tile_bufs(Ctx& ctx, unsigned tiles) {
+    return {ctx.arena.get<uint32_t>("tile_cnt", (size_t)tiles + 1),
+            ctx.arena.get<uint64_t>("tile_off", (size_t)tiles + 1)};
+}
+// tiles of four items per thread (at least one)
+inline unsigned quad_tiles(uint64_t n) {
+    return (unsigned)std::max<uint64_t>(1, (n + 4 * kBlock - 1) / (4 * kBlock));
 }
 
 // The weighted sweep (sample_weight): wrec = the records' fixed-point
@@ -2721,32 +2722,15 @@ void launch_count(hipStream_t s, const T* Xs, uint32_t R, const Cells& C, double
 #endif
 template <int D>
 constexpr int kWCountWpe = PD_WCOUNT_WPE ? PD_WCOUNT_WPE : (D <= 2 ? 8 : (D == 3 ? 6 : 5));
-template <typename T, int D, int M>
-void launch_count_weighted(hipStream_t s, const T* Xs, uint32_t R, const Cells& C, double eps,
-                           double eps2, float lo, float hi, uint32_t ms, int full,
-                           uint32_t rot_min, uint8_t* core, uint32_t* mn, const uint64_t* wrec) {
-    hipLaunchKernelGGL((count4_kernel<T, D, M, false, kWCountWpe<D>, false, true>), dim3(blocks(R)),
-                       dim3(kBlock), 0, s, Xs, R, C, eps, eps2, lo, hi, ms, full, rot_min, core, mn,
-                       (uint32_t*)nullptr, (unsigned long long*)nullptr, 0u, wrec,
-                       (uint64_t)ms << kWeightFrac);
-}
 
-// PD_OPT_COUNT_REPLAY (measurement): the shipped count sweep over `reps`
-// replicas of the R records (lane i sweeps record i % R), timed with its own
-// events into PD_T_COUNT_KERNEL.
-template <typename T, int D, int M>
-float replay_count(hipStream_t s, const T* Xs, uint32_t R, uint32_t reps, const Cells& C,
-                   double eps, double eps2, float lo, float hi, uint32_t ms, int full,
-                   uint32_t rot_min, uint8_t* core, uint32_t* mn, uint32_t* cnt) {
-    const uint64_t RL = (uint64_t)R * reps;
-    if (RL >= 0xFFFFFFFFull) throw Error(-1, "count replay: more than 2^32 - 1 lanes");
+// Milliseconds that `work`, queued on s, takes on the device (own events; syncs).
+template <typename F>
+float timed(hipStream_t s, F&& work) {
     hipEvent_t e0, e1;
     PD_HIP(hipEventCreate(&e0));
     PD_HIP(hipEventCreate(&e1));
     PD_HIP(hipEventRecord(e0, s));
-    hipLaunchKernelGGL((count4_kernel<T, D, M, false, kCountWpe, true>), dim3(blocks(RL)), dim3(kBlock), 0,
-                       s, Xs, (uint32_t)RL, C, eps, eps2, lo, hi, ms, full, rot_min, core, mn, cnt,
-                       (unsigned long long*)nullptr, R);
+    work();
     PD_HIP(hipEventRecord(e1, s));
     PD_HIP(hipEventSynchronize(e1));
     float msec = 0;
@@ -2754,15 +2738,6 @@ float replay_count(hipStream_t s, const T* Xs, uint32_t R, uint32_t reps, const 
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return msec;
-}
-
-template <typename T, int D, int M>
-void launch_border(hipStream_t s, const T* Xs, uint32_t NL, const uint32_t* list, const Cells& C,
-                   double eps, double eps2, float lo, float hi, const uint32_t* vals,
-                   const uint32_t* par, const uint32_t* gmin, uint32_t* key_out,
-                   uint32_t* rec_out = nullptr) {
-    hipLaunchKernelGGL((border4_kernel<T, D, M, kBorderWpe>), dim3(blocks(NL)), dim3(kBlock), 0, s, Xs, NL,
-                       list, C, eps, eps2, lo, hi, vals, par, gmin, key_out, rec_out);
 }
 
 // The record sort: the library's onesweep (rsort.hpp), stable, bits [0,
@@ -2810,16 +2785,6 @@ void sort_records(Ctx& ctx, K*& keys, uint32_t*& vals, K* keys2, uint32_t* vals2
 #endif
 }
 
-// Ordered compaction of record ids satisfying `pred` (keeps the spatial
-// order, so a wave's records stay neighbours).  Returns the count (syncs).
-template <typename Pred>
-uint32_t select_records(Ctx& ctx, const char* name, uint32_t R, Pred pred, uint32_t** out,
-                        hipStream_t s) {
-    uint32_t* list = ctx.arena.get<uint32_t>(name, R);
-    *out = list;
-    return (uint32_t)compact_ordered(ctx, "sel_cmp", (uint64_t)R, pred, list, nullptr, s);
-}
-
 // PD_CHECK_BOUNDS builds: after a checked kernel, read the violation record
 // and throw with the site and the first index (nothing in normal builds).
 void check_bounds(hipStream_t s, const char* kernel) {
@@ -2841,469 +2806,534 @@ void check_bounds(hipStream_t s, const char* kernel) {
 #endif
 }
 
-// Phase A: halo records, sort, cell directory, core counts, union-find,
-// component keys (marks 0..8).  Leaves its device state in ctx.st.
-template <typename T, int D, typename K, int M>
-void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t Gtot,
-           int key_bits, EvTimer& tm) {
-    hipStream_t s = a.stream;
-    const uint64_t n = (uint64_t)a.n;
-    const int P = a.P;
-    // key_of accumulates cell indices in double (exact below 2^53 cells)
-    if (Gtot >= (1ull << 53)) throw Error(-5, "eps grid of 2^53 cells or more");
-    tm.mark();   // 0
+// ---- phase A of the d <= 4 train: one function per timing slot, called in
+// order by run_a.  GridState is what a stage hands to the next ones (the
+// device buffers are the arena's); its typed layers add the cell keys (K) and
+// the coordinate rows (T), so a stage is templated only on what it uses.
+struct GridState {
+    hipStream_t s = nullptr;
+    uint64_t n = 0, Gtot = 0;
+    int P = 0, key_bits = 0;
+    uint32_t R = 0;                   // halo records
+    PartGrid* parts = nullptr;
+    // train_ctrs: [0] dup, [1] roots, [2] core, [3] border records, [8] big
+    // and [9] mid cells, [10] deferred pairs (zeroed by the halo pass)
+    uint32_t* ctrs = nullptr;
+    uint32_t* vals = nullptr;         // record -> point
+    uint32_t* dup_list = nullptr;     // records of points in several neighbourhoods
+    uint32_t* rep = nullptr;          // the merge's representative per point (P > 1)
+    uint64_t* wrec = nullptr;         // sample_weight: fixed-point weight per record
+    uint32_t* wbad = nullptr;         //   and the invalid-weight count
+    // cell directory
+    uint32_t* part_start = nullptr;
+    uint32_t* cstart = nullptr;
+    uint4* dir = nullptr;
+    uint4* pages = nullptr;           // paged directory (null: flat)
+    uint64_t W = 0;                   // directory words (flat: the whole grid; paged: occupied + terminal)
+    uint32_t* dncells = nullptr;      // occupied cells, on the device
+    uint32_t ncells = 0;              //   and on the host (stage_cells' one read)
+    // sweeps
+    double eps = 0, eps2 = 0;
+    float slo = -1.0f, shi = INFINITY;   // fp32 screening band (see Pred)
+    uint8_t* core = nullptr;
+    uint32_t* mn = nullptr;           // two smallest neighbours (uint2)
+    uint32_t* cnt_rec = nullptr;
+    unsigned long long* sst = nullptr;   // PD_OPT_SWEEP_STATS counters
+    uint32_t* par = nullptr;
+    uint32_t* gmin = nullptr;
+    Cells cells() const { return Cells{parts, part_start, P, dir, cstart, pages}; }
+};
+template <typename K>
+struct GridKeys : GridState {
+    K* keys = nullptr;    // (neighbourhood, cell) key per record
+    K* ckeys = nullptr;   // key of each occupied cell
+};
+template <typename T, typename K>
+struct GridTrain : GridKeys<K> {
+    const T* X = nullptr;
+    T* Xs = nullptr;      // coordinate rows in key order
+};
 
-    PartGrid* parts = ctx.arena.get<PartGrid>("parts", P);
-    const T* X = (const T*)a.X;
+// Marks 0 -> 1: grid and split-tree upload, halo tile counts, record write.
+template <typename T, int D, typename K>
+void stage_halo(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, GridTrain<T, K>& g) {
+    hipStream_t s = g.s;
+    const uint64_t n = g.n;
+    const int P = g.P;
+    g.parts = ctx.arena.get<PartGrid>("parts", P);
 
     // the split tree (pd_train_tree): ONE pinned block carries the grids and
     // the tree's tables (no sync between uploads)
     KdTree tree;
     if (!a.owner && a.tree_levels > 0) tree = kd_tree_shape(a.tree_levels, a.tree_sizes, a.tree_cur);
-    {
-        const size_t pb = (sizeof(PartGrid) * P + 15) & ~size_t(15);
-        const size_t tb = tree.nl ? kd_tree_bytes(tree) : 0;
-        char* h = (char*)pinned(ctx, pb + tb);
-        char* dt = tree.nl ? ctx.arena.get<char>("kd_tree", tb) : nullptr;
-        if (tree.nl)   // (validates the caller's tree: before any upload)
-            kd_tree_fill(tree, a.tree_sizes, a.tree_cur, a.tree_axis, a.tree_bound, a.tree_new, D, P,
-                         h + pb, dt);
-        std::memcpy(h, hparts.data(), sizeof(PartGrid) * P);
-        PD_HIP(hipMemcpyAsync(parts, h, sizeof(PartGrid) * P, hipMemcpyHostToDevice, s));
-        if (tree.nl) PD_HIP(hipMemcpyAsync(dt, h + pb, tb, hipMemcpyHostToDevice, s));
-        // (the block is next written by a D2H copy ordered after these on s,
-        // and read by the host only after a sync)
-    }
+    const size_t pb = (sizeof(PartGrid) * P + 15) & ~size_t(15);
+    const size_t tb = tree.nl ? kd_tree_bytes(tree) : 0;
+    char* h = (char*)pinned(ctx, pb + tb);
+    char* dt = tree.nl ? ctx.arena.get<char>("kd_tree", tb) : nullptr;
+    if (tree.nl)   // (validates the caller's tree: before any upload)
+        kd_tree_fill(tree, a.tree_sizes, a.tree_cur, a.tree_axis, a.tree_bound, a.tree_new, D, P,
+                     h + pb, dt);
+    std::memcpy(h, hparts.data(), sizeof(PartGrid) * P);
+    PD_HIP(hipMemcpyAsync(g.parts, h, sizeof(PartGrid) * P, hipMemcpyHostToDevice, s));
+    if (tree.nl) PD_HIP(hipMemcpyAsync(dt, h + pb, tb, hipMemcpyHostToDevice, s));
+    // (the block is next written by a D2H copy ordered after these on s,
+    // and read by the host only after a sync)
 
     // ---- halo records (R:dbscan/dbscan.py:136-151)
-    const unsigned htiles = (unsigned)std::max<uint64_t>(1, (n + 4 * kBlock - 1) / (4 * kBlock));
-    uint32_t* ctrs = ctx.arena.get<uint32_t>("train_ctrs", kCtrs);
+    const unsigned htiles = quad_tiles(n);
+    g.ctrs = ctx.arena.get<uint32_t>("train_ctrs", kCtrs);
     uint32_t* sort_hist = PD_SORT_ROCPRIM ? nullptr : ctx.arena.get<uint32_t>("rsort_hist", 8 * rsort::kRadix);
     // two passes: tile counts, scan, write
-    uint32_t* tcnt = ctx.arena.get<uint32_t>("tile_cnt", (size_t)htiles + 1);
-    uint64_t* toff = ctx.arena.get<uint64_t>("tile_off", (size_t)htiles + 1);
-    hipLaunchKernelGGL((halo_tile_kernel<T, D>), dim3(htiles), dim3(kBlock), 0, s, X, n, parts, P,
-                       tcnt, ctrs, sort_hist);
+    auto [tcnt, toff] = tile_bufs(ctx, htiles);
+    hipLaunchKernelGGL((halo_tile_kernel<T, D>), dim3(htiles), dim3(kBlock), 0, s, g.X, n, g.parts, P,
+                       tcnt, g.ctrs, sort_hist);
     const uint64_t R64 = tile_offsets(ctx, tcnt, htiles, toff, s, true);
     if (R64 >= 0xFFFFFFFEull) throw Error(-5, "more than 2^32-2 halo records on one device");
-    K* keys = ctx.arena.get<K>("keys", R64);
-    uint32_t* vals = ctx.arena.get<uint32_t>("vals", R64);
-    if (P <= 64)
-        hipLaunchKernelGGL((halo_write_kernel<T, D, K, true>), dim3(htiles), dim3(kBlock), 0, s, X,
-                           n, parts, P, a.owner, tree, toff, R64, keys, vals);
-    else
-        hipLaunchKernelGGL((halo_write_kernel<T, D, K, false>), dim3(htiles), dim3(kBlock), 0, s, X,
-                           n, parts, P, a.owner, tree, toff, R64, keys, vals);
+    g.keys = ctx.arena.get<K>("keys", R64);
+    g.vals = ctx.arena.get<uint32_t>("vals", R64);
+    hipLaunchKernelGGL((P <= 64 ? halo_write_kernel<T, D, K, true> : halo_write_kernel<T, D, K, false>),
+                       dim3(htiles), dim3(kBlock), 0, s, g.X, n, g.parts, P, a.owner, tree, toff, R64,
+                       g.keys, g.vals);
     PD_HIP(hipGetLastError());
     check_bounds(s, "halo_write_kernel");
-    const uint32_t R = (uint32_t)R64;
-    ctx.t.records = R;
-    K* keys2 = ctx.arena.get<K>("keys2", R);
-    uint32_t* vals2 = ctx.arena.get<uint32_t>("vals2", R);
-    tm.mark();   // 1
+    g.R = (uint32_t)R64;
+    ctx.t.records = g.R;
+}
 
-    // ---- shuffle by neighbourhood == sort by (neighbourhood, cell) key:
-    // the library's onesweep (rsort.hpp: stable, one kernel per 8-bit digit,
-    // C2 2.6 vs rocPRIM's 3.0 ms) over (key, id) pairs, then a gather of the
-    // coordinates into key order.  (Round 5 measured an MSD bucket sort that
-    // carries the coordinate rows instead — slower: C2 8.76 vs 5.91 ms, C4
-    // 84 vs 64 ms; DESIGN.md §6, tools/msd_probe.hip.  Also measured: C4's
-    // 37-bit keys in four passes of 10-bit digits, 1024-thread blocks —
-    // sort 46.1 vs 40.6 ms, profiles/r05_v3_ab_sort_10bit.txt.)
-    T* Xs = ctx.arena.get<T>("Xs", (size_t)R * Stride<D>::v);
-    uint32_t* dup_list = ctx.arena.get<uint32_t>("dup_list", R);
-    uint32_t* lcount = ctrs;   // dup, roots, core, border (zeroed by the halo pass)
+// Marks 1 -> 2: shuffle by neighbourhood == sort by (neighbourhood, cell) key:
+// the library's onesweep (rsort.hpp: stable, one kernel per 8-bit digit,
+// C2 2.6 vs rocPRIM's 3.0 ms) over (key, id) pairs; stage_gather then brings
+// the coordinates into key order.  (Round 5 measured an MSD bucket sort that
+// carries the coordinate rows instead — slower: C2 8.76 vs 5.91 ms, C4
+// 84 vs 64 ms; DESIGN.md §6, tools/msd_probe.hip.  Also measured: C4's
+// 37-bit keys in four passes of 10-bit digits, 1024-thread blocks —
+// sort 46.1 vs 40.6 ms, profiles/r05_v3_ab_sort_10bit.txt.)
+template <typename K>
+void stage_sort(Ctx& ctx, GridKeys<K>& g) {
+    K* keys2 = ctx.arena.get<K>("keys2", g.R);
+    uint32_t* vals2 = ctx.arena.get<uint32_t>("vals2", g.R);
+    sort_records<K>(ctx, g.keys, g.vals, keys2, vals2, (uint64_t)g.R, g.key_bits, g.s,
+                    /*hist_zeroed=*/!PD_SORT_ROCPRIM);   // by stage_halo's tile pass
+}
+
+// Marks 2 -> 3: coordinates into key order, the duplicated records' list,
+// and the sample-weight records.
+template <typename T, int D, typename K>
+void stage_gather(Ctx& ctx, TrainArgs& a, GridTrain<T, K>& g) {
+    hipStream_t s = g.s;
+    const uint64_t n = g.n;
+    const uint32_t R = g.R;
+    g.Xs = ctx.arena.get<T>("Xs", (size_t)R * Stride<D>::v);
+    g.dup_list = ctx.arena.get<uint32_t>("dup_list", R);
     // the merge's representative per point, initialised for the points of the
     // duplicated records only (by the gather, which lists them), not a fill over n
-    uint32_t* rep = P > 1 ? ctx.arena.get<uint32_t>("rep", n) : nullptr;
-    sort_records<K>(ctx, keys, vals, keys2, vals2, (uint64_t)R, key_bits, s,
-                    /*hist_zeroed=*/!PD_SORT_ROCPRIM);   // by the halo pass above
-    tm.mark();   // 2
-    hipLaunchKernelGGL((gather_kernel<T, D>), dim3(blocks(R)), dim3(kBlock), 0, s, X, (uint64_t)R,
-                       vals, Xs, dup_list, lcount, rep);
+    g.rep = g.P > 1 ? ctx.arena.get<uint32_t>("rep", n) : nullptr;
+    hipLaunchKernelGGL((gather_kernel<T, D>), dim3(blocks(R)), dim3(kBlock), 0, s, g.X, (uint64_t)R,
+                       g.vals, g.Xs, g.dup_list, g.ctrs, g.rep);
     // sample_weight: the fixed-point weights (their validity count is read
-    // back at the cell-count sync below), then each record's weight
-    uint64_t* wrec = nullptr;
-    uint32_t* wbad = nullptr;
+    // back at the cell-count sync, stage_cells), then each record's weight
     if (a.weight) {
         uint64_t* wfix = ctx.arena.get<uint64_t>("weight_fix", n);
-        wrec = ctx.arena.get<uint64_t>("weight_rec", R);
-        wbad = ctx.arena.get<uint32_t>("weight_bad", 4);
-        PD_HIP(hipMemsetAsync(wbad, 0, sizeof(uint32_t), s));
+        g.wrec = ctx.arena.get<uint64_t>("weight_rec", R);
+        g.wbad = ctx.arena.get<uint32_t>("weight_bad", 4);
+        PD_HIP(hipMemsetAsync(g.wbad, 0, sizeof(uint32_t), s));
         hipLaunchKernelGGL(weight_fix_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, a.weight, n, wfix,
-                           wbad);
+                           g.wbad);
         if (R)
-            hipLaunchKernelGGL(record_weight_kernel, dim3(blocks(R)), dim3(kBlock), 0, s, wfix, vals,
-                               (uint64_t)R, n, wrec);
+            hipLaunchKernelGGL(record_weight_kernel, dim3(blocks(R)), dim3(kBlock), 0, s, wfix, g.vals,
+                               (uint64_t)R, n, g.wrec);
         PD_HIP(hipGetLastError());
         check_bounds(s, "record_weight_kernel");
     }
-    tm.mark();   // 3
+}
 
-    // ---- cell directory
-#ifndef PD_NC_SYNC
-#define PD_NC_SYNC 1   // (A/B builds: 0 = directory bits over the records, no sync)
-#endif
-    uint32_t* part_start = ctx.arena.get<uint32_t>("part_start", P + 1);
-    hipLaunchKernelGGL((part_start_kernel<K>), dim3((P + 1 + 63) / 64), dim3(64), 0, s, keys,
-                       (uint64_t)R, parts, P, part_start);
-    uint32_t* cstart = ctx.arena.get<uint32_t>("cstart", (size_t)R + 1);
-    K* ckeys = ctx.arena.get<K>("cell_keys", (size_t)R + 1);   // key of each occupied cell
-    uint32_t* dncells = ctx.arena.get<uint32_t>("ncells", 4);
+// per-tile popcount prefix over a uint4 array's (x, y) bits into .z
+uint64_t prefix_words(Ctx& ctx, hipStream_t s, uint4* d, uint64_t nw, bool read_total) {
+    const unsigned wtiles = quad_tiles(nw);
+    auto [tcnt, toff] = tile_bufs(ctx, wtiles);
+    hipLaunchKernelGGL(dir_tile_kernel, dim3(wtiles), dim3(kBlock), 0, s, d, nw, tcnt);
+    const uint64_t tot = tile_offsets(ctx, tcnt, wtiles, toff, s, read_total);
+    hipLaunchKernelGGL(dir_write_kernel, dim3(wtiles), dim3(kBlock), 0, s, d, nw, toff);
+    return tot;
+}
+
+// The directory over the occupied cells' keys: flat (a word per 64 cells of
+// the whole grid) or paged (a page per 4096 cells, then the occupied words).
+// Its passes launch over the cells (g.ncells), not the records.
+template <typename K>
+void build_directory(Ctx& ctx, bool paged, GridKeys<K>& g) {
+    hipStream_t s = g.s;
+    const dim3 cgrid(blocks(g.ncells)), blk(kBlock);
+    // word ids (keys >> 6) and page ids (keys >> 12) below 2^31 take the
+    // kernels' 32-bit form
+    const bool words32 = sizeof(K) == 4 || g.key_bits <= 37;
+    const bool pages32 = sizeof(K) == 4 || g.key_bits <= 43;
+    if (!paged) {
+        g.W = (g.Gtot >> 6) + 2;
+        g.dir = ctx.arena.get<uint4>("dir", g.W);
+        PD_HIP(hipMemsetAsync(g.dir, 0, sizeof(uint4) * g.W, s));
+        if (g.R)
+            hipLaunchKernelGGL((words32 ? dir_bits_kernel<K, 0, true> : dir_bits_kernel<K, 0, false>),
+                               cgrid, blk, 0, s, g.ckeys, g.dncells, g.dir);
+        prefix_words(ctx, s, g.dir, g.W, false);
+        return;
+    }
+    // pages: word masks, then the occupied words before each page (the
+    // total sizes the word array: one sync); then the words themselves
+    const uint64_t NP = (g.Gtot >> 12) + 2;
+    g.pages = ctx.arena.get<uint4>("dir_pages", NP);
+    PD_HIP(hipMemsetAsync(g.pages, 0, sizeof(uint4) * NP, s));
+    if (g.R)
+        hipLaunchKernelGGL((pages32 ? dir_bits_kernel<K, 6, true> : dir_bits_kernel<K, 6, false>),
+                           cgrid, blk, 0, s, g.ckeys, g.dncells, g.pages);
+    g.W = prefix_words(ctx, s, g.pages, NP, true) + 1;
+    g.dir = ctx.arena.get<uint4>("dir", g.W);
+    if (g.R)
+        hipLaunchKernelGGL((words32 ? word_write_kernel<K, true> : word_write_kernel<K, false>), cgrid,
+                           blk, 0, s, g.ckeys, g.dncells, g.pages, g.dir);
+    else
+        PD_HIP(hipMemsetAsync(g.dir, 0, sizeof(uint4), s));
+}
+
+// Marks 3 -> 4: cell starts, the train's one host read of the cell count,
+// the directory.
+template <typename K>
+void stage_cells(Ctx& ctx, TrainArgs& a, GridKeys<K>& g) {
+    hipStream_t s = g.s;
+    const uint32_t R = g.R;
+    g.part_start = ctx.arena.get<uint32_t>("part_start", g.P + 1);
+    hipLaunchKernelGGL((part_start_kernel<K>), dim3((g.P + 1 + 63) / 64), dim3(64), 0, s, g.keys,
+                       (uint64_t)R, g.parts, g.P, g.part_start);
+    g.cstart = ctx.arena.get<uint32_t>("cstart", (size_t)R + 1);
+    g.ckeys = ctx.arena.get<K>("cell_keys", (size_t)R + 1);
+    g.dncells = ctx.arena.get<uint32_t>("ncells", 4);
     if (R) {
-        const unsigned ctiles = (unsigned)((R + 4 * kBlock - 1) / (4 * kBlock));
-        uint32_t* ccnt = ctx.arena.get<uint32_t>("tile_cnt", (size_t)ctiles + 1);
-        uint64_t* coff = ctx.arena.get<uint64_t>("tile_off", (size_t)ctiles + 1);
-        hipLaunchKernelGGL((cell_tile_kernel<K>), dim3(ctiles), dim3(kBlock), 0, s, keys,
-                           (uint64_t)R, ccnt);
-        tile_offsets(ctx, ccnt, ctiles, coff, s, false);
-        hipLaunchKernelGGL((cell_write_kernel<K>), dim3(ctiles), dim3(kBlock), 0, s, keys,
-                           (uint64_t)R, coff, cstart, ckeys, dncells);
+        const unsigned ctiles = quad_tiles(R);
+        auto [tcnt, toff] = tile_bufs(ctx, ctiles);
+        hipLaunchKernelGGL((cell_tile_kernel<K>), dim3(ctiles), dim3(kBlock), 0, s, g.keys,
+                           (uint64_t)R, tcnt);
+        tile_offsets(ctx, tcnt, ctiles, toff, s, false);
+        hipLaunchKernelGGL((cell_write_kernel<K>), dim3(ctiles), dim3(kBlock), 0, s, g.keys,
+                           (uint64_t)R, toff, g.cstart, g.ckeys, g.dncells);
     } else {
-        PD_HIP(hipMemsetAsync(cstart, 0, sizeof(uint32_t), s));
-        PD_HIP(hipMemsetAsync(dncells, 0, sizeof(uint32_t), s));
+        PD_HIP(hipMemsetAsync(g.cstart, 0, sizeof(uint32_t), s));
+        PD_HIP(hipMemsetAsync(g.dncells, 0, sizeof(uint32_t), s));
     }
-    // the cell count on the host (one sync): the directory passes then launch
-    // over the cells, not the records (C2: 57 % of the waves, C4: 66 %)
-    uint64_t cgrid0 = R;
-#if PD_NC_SYNC
-    if (R) {
-        uint32_t* hnc = (uint32_t*)((char*)pinned(ctx, 16) + 8);
-        PD_HIP(hipMemcpyAsync(hnc, dncells, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        // (sample_weight: the invalid-weight count rides on this sync)
-        uint32_t* hwb = hnc + 1;
-        if (wbad) PD_HIP(hipMemcpyAsync(hwb, wbad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    // the cell count on the host (one sync): the directory passes and the
+    // link's per-cell kernels then launch over the cells, not the records
+    // (C2: 57 % of the waves, C4: 66 %), the auto window is chosen from it
+    // and finish() reports it.  (sample_weight: the invalid-weight count rides
+    // on this sync.)  Both words are taken out of the pinned block at once:
+    // tile_offsets reuses it.
+    if (R || g.wbad) {
+        uint32_t* h = (uint32_t*)pinned(ctx, 2 * sizeof(uint32_t));
+        PD_HIP(hipMemcpyAsync(h, g.dncells, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (g.wbad) PD_HIP(hipMemcpyAsync(h + 1, g.wbad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         sync(s);
-        cgrid0 = std::max<uint64_t>(1, std::min<uint64_t>(*hnc, R));
-        if (wbad && *hwb)
-            throw Error(-1, "sample_weight: " + std::to_string(*hwb) +
-                                " value(s) not finite or outside [0, 2^31]");
-        wbad = nullptr;
-    }
-#endif
-    if (wbad) {   // (no cell-count sync in this build / an empty record set)
-        uint32_t* hwb = (uint32_t*)pinned(ctx, sizeof(uint32_t));
-        PD_HIP(hipMemcpyAsync(hwb, wbad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        sync(s);
-        if (*hwb)
-            throw Error(-1, "sample_weight: " + std::to_string(*hwb) +
+        const uint32_t nc = h[0], bad = g.wbad ? h[1] : 0u;
+        g.ncells = R ? std::max(1u, std::min(nc, R)) : 0u;
+        if (bad)
+            throw Error(-1, "sample_weight: " + std::to_string(bad) +
                                 " value(s) not finite or outside [0, 2^31]");
     }
-    // per-tile popcount prefix over a uint4 array's (x, y) bits into .z
-    auto prefix_words = [&](uint4* d, uint64_t nw, bool read_total) -> uint64_t {
-        const unsigned wtiles = (unsigned)std::max<uint64_t>(1, (nw + 4 * kBlock - 1) / (4 * kBlock));
-        uint32_t* wcnt = ctx.arena.get<uint32_t>("tile_cnt", (size_t)wtiles + 1);
-        uint64_t* woff = ctx.arena.get<uint64_t>("tile_off", (size_t)wtiles + 1);
-        hipLaunchKernelGGL(dir_tile_kernel, dim3(wtiles), dim3(kBlock), 0, s, d, nw, wcnt);
-        const uint64_t tot = tile_offsets(ctx, wcnt, wtiles, woff, s, read_total);
-        hipLaunchKernelGGL(dir_write_kernel, dim3(wtiles), dim3(kBlock), 0, s, d, nw, woff);
-        return tot;
-    };
-    uint64_t W;            // directory words (flat: the whole grid; paged: occupied + terminal)
-    uint4* dir;
-    uint4* pages = nullptr;
-    if (!a.dir_paged) {
-        W = (Gtot >> 6) + 2;
-        dir = ctx.arena.get<uint4>("dir", W);
-        PD_HIP(hipMemsetAsync(dir, 0, sizeof(uint4) * W, s));
-        if (R) {
-            if (sizeof(K) == 4 || key_bits <= 37)   // word ids < 2^31
-                hipLaunchKernelGGL((dir_bits_kernel<K, 0, true>), dim3(blocks(cgrid0)), dim3(kBlock), 0, s,
-                                   ckeys, dncells, dir);
-            else
-                hipLaunchKernelGGL((dir_bits_kernel<K, 0, false>), dim3(blocks(cgrid0)), dim3(kBlock), 0,
-                                   s, ckeys, dncells, dir);
-        }
-        prefix_words(dir, W, false);
-    } else {
-        // pages: word masks, then the occupied words before each page (the
-        // total sizes the word array: one sync); then the words themselves
-        const uint64_t NP = (Gtot >> 12) + 2;
-        pages = ctx.arena.get<uint4>("dir_pages", NP);
-        PD_HIP(hipMemsetAsync(pages, 0, sizeof(uint4) * NP, s));
-        if (R) {
-            if (sizeof(K) == 4 || key_bits <= 43)   // page ids < 2^31
-                hipLaunchKernelGGL((dir_bits_kernel<K, 6, true>), dim3(blocks(cgrid0)), dim3(kBlock), 0, s,
-                                   ckeys, dncells, pages);
-            else
-                hipLaunchKernelGGL((dir_bits_kernel<K, 6, false>), dim3(blocks(cgrid0)), dim3(kBlock), 0,
-                                   s, ckeys, dncells, pages);
-        }
-        // (the word pass launches over the cells too; without the count sync
-        // it rides on this one, beside the total in the pinned block)
-        if (R && !PD_NC_SYNC)
-            PD_HIP(hipMemcpyAsync((char*)pinned(ctx, 16) + 8, dncells, sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, s));
-        const uint64_t nw = prefix_words(pages, NP, true);
-        W = nw + 1;
-        dir = ctx.arena.get<uint4>("dir", W);
-        if (R)
-        {
-            const uint32_t nch = *(const uint32_t*)((const char*)pinned(ctx, 16) + 8);
-            const uint64_t wg = std::max<uint64_t>(1, std::min<uint64_t>(nch, R));
-            if (sizeof(K) == 4 || key_bits <= 37)   // word ids < 2^31
-                hipLaunchKernelGGL((word_write_kernel<K, true>), dim3(blocks(wg)), dim3(kBlock), 0, s,
-                                   ckeys, dncells, pages, dir);
-            else
-                hipLaunchKernelGGL((word_write_kernel<K, false>), dim3(blocks(wg)), dim3(kBlock), 0, s,
-                                   ckeys, dncells, pages, dir);
-        }
-        else
-            PD_HIP(hipMemsetAsync(dir, 0, sizeof(uint4), s));
-    }
-    ctx.t.dir_words = (int64_t)W;
+    build_directory<K>(ctx, a.dir_paged, g);
+    ctx.t.dir_words = (int64_t)g.W;
     PD_HIP(hipGetLastError());
-    tm.mark();   // 4
+}
 
-    Cells C{parts, part_start, P, dir, cstart, pages};
-    const double eps = a.eps, eps2 = a.eps * a.eps;
+// Marks 4 -> 5: the count sweep.  It runs at 8 waves per SIMD (64 VGPRs); its
+// instrumented form (PD_OPT_SWEEP_STATS) without the register cap; the
+// weighted form at kWCountWpe<D>.
+template <typename T, int D, int M>
+void stage_count(Ctx& ctx, TrainArgs& a, GridState& g, const T* Xs) {
+    hipStream_t s = g.s;
+    const uint32_t R = g.R;
+    g.eps = a.eps;
+    g.eps2 = a.eps * a.eps;
     // fp32 screening band (see Pred): thresholds rounded outward
-    float slo = -1.0f, shi = INFINITY;
-    {
-        const double thr = a.metric == 0 ? eps2 : eps;
-        if (std::is_same<T, float>::value && thr > 1e-30 && thr < 1e30 && ctx.screen) {
-            slo = std::nextafter((float)(thr * (1.0 - 1.0 / 262144.0)), 0.0f);
-            shi = std::nextafter((float)(thr * (1.0 + 1.0 / 262144.0)), INFINITY);
-        }
+    const double thr = a.metric == 0 ? g.eps2 : g.eps;
+    if (std::is_same<T, float>::value && thr > 1e-30 && thr < 1e30 && ctx.screen) {
+        g.slo = std::nextafter((float)(thr * (1.0 - 1.0 / 262144.0)), 0.0f);
+        g.shi = std::nextafter((float)(thr * (1.0 + 1.0 / 262144.0)), INFINITY);
     }
-    uint8_t* core = ctx.arena.get<uint8_t>("core", R);
-    uint32_t* mn = ctx.arena.get<uint32_t>("minnbr", 2 * (size_t)R);   // two smallest (uint2)
-    uint32_t* cnt_rec = a.counts ? ctx.arena.get<uint32_t>("cnt_rec", R) : nullptr;
-    unsigned long long* sst = nullptr;
+    g.core = ctx.arena.get<uint8_t>("core", R);
+    g.mn = ctx.arena.get<uint32_t>("minnbr", 2 * (size_t)R);
+    g.cnt_rec = a.counts ? ctx.arena.get<uint32_t>("cnt_rec", R) : nullptr;
     if (ctx.sweep_stats) {
-        sst = ctx.arena.get<unsigned long long>("sweep_stats", 10);
-        PD_HIP(hipMemsetAsync(sst, 0, sizeof(unsigned long long) * 10, s));
-    }
-    // the auto window's cell count (link step 2) is copied back before the
-    // count sweep and waited for after it is queued: the host learns it while
-    // the sweep runs, and the window union launches with no gap
-    uint32_t* h_nc = nullptr;
-    hipEvent_t ev_nc = nullptr;
-    if (R && ctx.centre_window < 0) {
-        h_nc = (uint32_t*)pinned(ctx, sizeof(uint32_t));
-        PD_HIP(hipEventCreateWithFlags(&ev_nc, hipEventDisableTiming));
-        PD_HIP(hipMemcpyAsync(h_nc, dncells, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        PD_HIP(hipEventRecord(ev_nc, s));
+        g.sst = ctx.arena.get<unsigned long long>("sweep_stats", 10);
+        PD_HIP(hipMemsetAsync(g.sst, 0, sizeof(unsigned long long) * 10, s));
     }
     if (R) {
+        const uint32_t ms = (uint32_t)a.min_samples;
+        const int full = ctx.full_counts ? 1 : 0;
         const uint32_t rot = ctx.count_rotate ? (uint32_t)ctx.count_rotate : 0xFFFFFFFFu;
-        if (wrec)
-            launch_count_weighted<T, D, M>(s, Xs, R, C, eps, eps2, slo, shi, (uint32_t)a.min_samples,
-                                           ctx.full_counts ? 1 : 0, rot, core, mn, wrec);
-        else if (sst)
-            launch_count<T, D, M, true>(s, Xs, R, C, eps, eps2, slo, shi, (uint32_t)a.min_samples,
-                                        ctx.full_counts ? 1 : 0, rot, core, mn, cnt_rec, sst);
-        else
-            launch_count<T, D, M, false>(s, Xs, R, C, eps, eps2, slo, shi, (uint32_t)a.min_samples,
-                                         ctx.full_counts ? 1 : 0, rot, core, mn, cnt_rec, sst);
-        if (ctx.count_replay > 0 && !sst && !wrec)
-            ctx.t.count_kernel = replay_count<T, D, M>(
-                s, Xs, R, (uint32_t)ctx.count_replay, C, eps, eps2, slo, shi,
-                (uint32_t)a.min_samples, ctx.full_counts ? 1 : 0, rot, core, mn, cnt_rec);
-    }
-    PD_HIP(hipGetLastError());
-    tm.mark();   // 5
-
-    uint32_t* par = ctx.arena.get<uint32_t>("parent", R);
-    uint32_t* gmin = ctx.arena.get<uint32_t>("gmin", R);
-    if (R) {
-        // (1) forest from the count pass's two smallest neighbours
-        uint32_t* wroot = ctx.arena.get<uint32_t>("word_root", W);
-        // (single device: the n-bit component-key map of rank_roots, zeroed here)
-        // (+ the root lists' counters after it, from a 128-B boundary)
-        const uint64_t NW = a.phase == 0 ? (n + 31) / 32 : 0;
-        const uint64_t NWz = NW ? ((NW + 31) & ~uint64_t(31)) + kRootLists * kRootCntStride : 0;
-        uint32_t* kbits = NW ? ctx.arena.get<uint32_t>("key_bits", NWz) : nullptr;
-        hipLaunchKernelGGL(init_kernel,
-                           dim3(sub_blocks(std::max<uint64_t>(std::max<uint64_t>(R, W), NWz), kInitSub)),
-                           dim3(kBlock), 0, s, R, core, mn, 1, par, gmin, wroot, (uint64_t)W, kbits, NWz);
-        check_bounds(s, "init_kernel");
-        // (2) window union.  Auto window (PD_OPT_CENTRE_WINDOW < 0): sparse
-        // cells (a few records each, C2: 2.3) gain little from the window
-        // beyond the fused flatten, so a short one is cheapest (C2 link 6.59
-        // -> 5.96 ms at 16 -> 4; round 5: 5.45 / 5.33 / 5.42 ms at 4 / 2 / 1,
-        // and 56 ms with the flatten alone); dense cells (C4 city centres)
-        // want the long one (C4 link 71.5 -> 60.6 ms at 4 -> 16)
-        int cw = ctx.centre_window;
-        // the per-cell kernels' grid: the cells when the host knows their
-        // count (the auto window), else the records (a bound: the kernels
-        // read the count on the device and leave past it)
-        uint64_t cgrid = R;
-        if (cw < 0) {
-            PD_HIP(hipEventSynchronize(ev_nc));
-            (void)hipEventDestroy(ev_nc);
-            const uint32_t nc = *h_nc ? *h_nc : 1u;
-            cgrid = std::min<uint64_t>(nc, R);
-            // records per occupied cell: <= 2.5 -> 2 (C2: 2.32), <= 8 -> 8
-            // (C4: 2.96, dense cities in sparse noise: link 37.1 / 32.2 /
-            // 56.3 / 142.9 ms at 4 / 8 / 16 / 32; C1: 4.96, 0.58 / 0.60 /
-            // 0.61 ms at 4 / 8 / 16), else 16
-            cw = 2 * (uint64_t)R <= 5ull * nc ? 2 : ((uint64_t)R <= 8ull * nc ? 8 : 16);
-        }
-        auto go = [&](auto Wc) {
-            constexpr int Wv = decltype(Wc)::value;
-            // a block covers kBlock records per group of its waves
-            constexpr int Kw = window_groups((int)sizeof(T), D, Wv);
-            const unsigned wb = blocks(((uint64_t)R + Kw - 1) / Kw);
-            if (sst)
-                hipLaunchKernelGGL((window_uf_kernel<T, D, M, Wv, true>), dim3(wb), dim3(kBlock), 0,
-                                   s, Xs, R, eps, eps2, slo, shi, par, sst);
-            else
-                hipLaunchKernelGGL((window_uf_kernel<T, D, M, Wv, false>), dim3(wb), dim3(kBlock), 0,
-                                   s, Xs, R, eps, eps2, slo, shi, par, sst);
+        // one launch form for every instantiation of the sweep: `lanes` lanes
+        // (lane i sweeps record i, or i % rmod in a replay; only the ST form
+        // reads the stats pointer)
+        auto sweep = [&](auto kernel, uint32_t lanes, uint32_t* cnt, uint32_t rmod,
+                         const uint64_t* wrec, uint64_t wthr) {
+            hipLaunchKernelGGL(kernel, dim3(blocks(lanes)), dim3(kBlock), 0, s, Xs, lanes, g.cells(),
+                               g.eps, g.eps2, g.slo, g.shi, ms, full, rot, g.core, g.mn, cnt, g.sst,
+                               rmod, wrec, wthr);
         };
-        if (cw <= 2)
-            go(std::integral_constant<int, 2>{});
-        else if (cw <= 4)
-            go(std::integral_constant<int, 4>{});
-        else if (cw <= 8)
-            go(std::integral_constant<int, 8>{});
-        else if (cw <= 16)
-            go(std::integral_constant<int, 16>{});
-        else if (cw <= 32)
-            go(std::integral_constant<int, 32>{});
+        if (g.wrec)   // wthr = min_samples << 20; no counts, no stats in the weighted form
+            sweep(count4_kernel<T, D, M, false, kWCountWpe<D>, false, true>, R, nullptr, 0u, g.wrec,
+                  (uint64_t)ms << kWeightFrac);
         else
-            go(std::integral_constant<int, 64>{});
-        uint32_t* croot = ctx.arena.get<uint32_t>("cell_root", R);
-        {   // (3) cell and word roots in one pass
-            uint32_t* big = ctx.arena.get<uint32_t>("big_cells", R / (kWordBig + 1) + 1);
-            uint32_t* mid = ctx.arena.get<uint32_t>("mid_cells", R / (kMidCell + 1) + 1);
-            uint32_t* nbig = ctrs + 8;   // [0] big, [1] mid (zeroed by the halo pass)
-            // (wroot starts at kNone: init_kernel)
-            if ((uint64_t)W < 0xFFFFFFFFull)   // directory slots < 2^32 - 1
-                hipLaunchKernelGGL((cell_word_root_kernel<K, true>), dim3(blocks(cgrid)), dim3(kBlock), 0,
-                                   s, cstart, dncells, ckeys, par, croot, wroot, mid, nbig + 1, big,
-                                   nbig, pages);
-            else
-                hipLaunchKernelGGL((cell_word_root_kernel<K, false>), dim3(blocks(cgrid)), dim3(kBlock),
-                                   0, s, cstart, dncells, ckeys, par, croot, wroot, mid, nbig + 1,
-                                   big, nbig, pages);
-            hipLaunchKernelGGL((mid_cell_word_root_kernel<K>), dim3(2048), dim3(kBlock), 0, s,
-                               cstart, ckeys, mid, nbig + 1, par, croot, wroot, pages);
-            hipLaunchKernelGGL((big_cell_word_root_kernel<K>), dim3(1024), dim3(kBlock), 0, s,
-                               cstart, ckeys, big, nbig, par, croot, wroot, pages);
+            sweep(g.sst ? count4_kernel<T, D, M, true, 1> : count4_kernel<T, D, M, false, kCountWpe>,
+                  R, g.cnt_rec, 0u, nullptr, 0);
+        // PD_OPT_COUNT_REPLAY (measurement): the shipped count sweep over
+        // `count_replay` replicas of the R records (lane i sweeps record
+        // i % R), timed with its own events into PD_T_COUNT_KERNEL.
+        if (ctx.count_replay > 0 && !g.sst && !g.wrec) {
+            const uint64_t RL = (uint64_t)R * (uint32_t)ctx.count_replay;
+            if (RL >= 0xFFFFFFFFull) throw Error(-1, "count replay: more than 2^32 - 1 lanes");
+            ctx.t.count_kernel = timed(s, [&] {
+                sweep(count4_kernel<T, D, M, false, kCountWpe, true>, (uint32_t)RL, g.cnt_rec, R,
+                      nullptr, 0);
+            });
         }
-        const uint32_t pcap = (uint32_t)std::min<uint64_t>(R, 64ull << 20);
-        uint2* plist = ctx.arena.get<uint2>("pair_list", pcap);
-        uint32_t* pcount = ctrs + 10;   // (zeroed by the halo pass)
-        // (4) verify: screen every cell, then work on the flagged ones only
-        const unsigned vtiles = blocks(cgrid);
-        uint8_t* vflag = ctx.arena.get<uint8_t>("verify_flags", R);
-        uint32_t* vlist = ctx.arena.get<uint32_t>("verify_list", R);
-        uint32_t* vcnt = ctx.arena.get<uint32_t>("tile_cnt", (size_t)vtiles + 1);
-        uint64_t* voff = ctx.arena.get<uint64_t>("tile_off", (size_t)vtiles + 1);
-        if (ctx.verify_fused) {
-            // one pass over every cell: the screen's test inline (no flags,
-            // no list, no scan, no host read of the flagged count)
-            hipLaunchKernelGGL((cell_verify_kernel<T, D, M, K>), dim3(vtiles), dim3(kBlock), 0, s,
-                               Xs, keys, nullptr, 0u, croot, wroot, C, xsub_of(ctx), eps, eps2,
-                               slo, shi, par, plist, pcap, pcount, sst, dncells);
-        } else {
-            hipLaunchKernelGGL((verify_screen_kernel<D, K>), dim3(vtiles), dim3(kBlock), 0, s, keys,
-                               dncells, croot, wroot, C, xsub_of(ctx), vflag, vcnt);
-            const uint32_t NV = (uint32_t)tile_offsets(ctx, vcnt, vtiles, voff, s, true);
-            if (NV) {
-                hipLaunchKernelGGL(flag_list_kernel, dim3(vtiles), dim3(kBlock), 0, s, vflag, dncells,
-                                   voff, vlist);
-                hipLaunchKernelGGL((cell_verify_kernel<T, D, M, K>), dim3(blocks(NV)), dim3(kBlock), 0,
-                                   s, Xs, keys, vlist, NV, croot, wroot, C, xsub_of(ctx), eps, eps2,
-                                   slo, shi, par, plist, pcap, pcount, sst, nullptr);
-            }
-        }
-        hipLaunchKernelGGL((pair_kernel<T, D, M>), dim3(std::min(blocks(pcap), 4096u)), dim3(kBlock), 0, s, Xs, plist,
-                           pcount, pcap, cstart, croot, eps, eps2, slo, shi, par);
     }
     PD_HIP(hipGetLastError());
-    tm.mark();   // 6
-    if (P > 1 && R) {
-        // the merge touches only the records of points in several neighbourhoods
-        const unsigned gb = std::min(blocks(R), 2048u);
-        hipLaunchKernelGGL(rep_kernel, dim3(gb), dim3(kBlock), 0, s, dup_list, lcount, vals, par,
-                           rep);
-        hipLaunchKernelGGL(merge_kernel, dim3(gb), dim3(kBlock), 0, s, dup_list, lcount, vals, rep,
-                           par);
-    }
-    tm.mark();   // 7
-    if (R) {
-        // single device: the component keys are ranked here (labels);
-        // sharded: keys stay global ids (merge first)
-        // (gmin starts at kNone: init_kernel)
-        const unsigned rb = sub_blocks(R, kRootSub);
-        const uint32_t seg = ((rb + kRootLists - 1) / kRootLists) * (uint32_t)(kRootSub * kBlock);
-        const uint64_t NW = a.phase == 0 ? (n + 31) / 32 : 0;
-        uint32_t* rlist = NW ? ctx.arena.get<uint32_t>("root_list", (size_t)seg * kRootLists) : nullptr;
-        uint32_t* rcnt = NW ? ctx.arena.get<uint32_t>("key_bits", 1) + ((NW + 31) & ~uint64_t(31))
-                            : nullptr;   // (zeroed by init_kernel)
-        hipLaunchKernelGGL(roots_kernel, dim3(rb), dim3(kBlock), 0, s, R, vals, a.gid, par, gmin, rlist,
-                           rcnt, seg, lcount + 1, ctx.sweep_stats ? 1 : 0);
-        if (a.phase == 0) {
-            // rank the component keys on the device; the component count is
-            // read with the train's last copy back (finish)
-            uint32_t* kbits = ctx.arena.get<uint32_t>("key_bits", 1);
-            uint32_t* kpre = ctx.arena.get<uint32_t>("key_pre", NW);
-            const unsigned gb = kRootLists * 16;
-            hipLaunchKernelGGL(root_mark_kernel, dim3(gb), dim3(kBlock), 0, s, rlist, rcnt, seg, gmin,
-                               kbits);
-            rocprim::transform_iterator<const uint32_t*, PopcOp, uint32_t> pc(kbits, PopcOp{});
-            size_t tb = 0;
-            PD_HIP(rocprim::exclusive_scan(nullptr, tb, pc, kpre, 0u, (size_t)NW,
-                                           rocprim::plus<uint32_t>(), s));
-            void* tmp = ctx.arena.get<char>("key_scan_tmp", tb);
-            PD_HIP(rocprim::exclusive_scan(tmp, tb, pc, kpre, 0u, (size_t)NW,
-                                           rocprim::plus<uint32_t>(), s));
-            hipLaunchKernelGGL(root_rank_kernel, dim3(gb), dim3(kBlock), 0, s, rlist, rcnt, seg, kbits,
-                               kpre, NW, gmin, lcount + 1);
-        } else if (ctx.sweep_stats) {
-            uint32_t* h = (uint32_t*)pinned(ctx, sizeof(uint32_t) * 4);
-            PD_HIP(hipMemcpyAsync(h, lcount + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            sync(s);
-            ctx.t.core_records = h[0];
-        }
-    }
-    ctx.st.n_roots = 0;   // single device: set by finish
-    PD_HIP(hipGetLastError());
-    tm.mark();   // 8
+}
 
+// Link step 2, the window union.  Auto window (PD_OPT_CENTRE_WINDOW < 0):
+// sparse cells (a few records each, C2: 2.3) gain little from the window
+// beyond the fused flatten, so a short one is cheapest (C2 link 6.59
+// -> 5.96 ms at 16 -> 4; round 5: 5.45 / 5.33 / 5.42 ms at 4 / 2 / 1,
+// and 56 ms with the flatten alone); dense cells (C4 city centres)
+// want the long one (C4 link 71.5 -> 60.6 ms at 4 -> 16)
+template <typename T, int D, int M>
+void window_union(Ctx& ctx, GridState& g, const T* Xs) {
+    const uint64_t R = g.R, nc = g.ncells;
+    int cw = ctx.centre_window;
+    // records per occupied cell: <= 2.5 -> 2 (C2: 2.32), <= 8 -> 8
+    // (C4: 2.96, dense cities in sparse noise: link 37.1 / 32.2 /
+    // 56.3 / 142.9 ms at 4 / 8 / 16 / 32; C1: 4.96, 0.58 / 0.60 /
+    // 0.61 ms at 4 / 8 / 16), else 16
+    if (cw < 0) cw = 2 * R <= 5 * nc ? 2 : (R <= 8 * nc ? 8 : 16);
+    auto go = [&](auto Wc) {
+        constexpr int Wv = decltype(Wc)::value;
+        // a block covers kBlock records per group of its waves
+        constexpr int Kw = window_groups((int)sizeof(T), D, Wv);
+        const unsigned wb = blocks((R + Kw - 1) / Kw);
+        hipLaunchKernelGGL((g.sst ? window_uf_kernel<T, D, M, Wv, true>
+                                  : window_uf_kernel<T, D, M, Wv, false>),
+                           dim3(wb), dim3(kBlock), 0, g.s, Xs, g.R, g.eps, g.eps2, g.slo, g.shi, g.par,
+                           g.sst);
+    };
+    if (cw <= 2)
+        go(std::integral_constant<int, 2>{});
+    else if (cw <= 4)
+        go(std::integral_constant<int, 4>{});
+    else if (cw <= 8)
+        go(std::integral_constant<int, 8>{});
+    else if (cw <= 16)
+        go(std::integral_constant<int, 16>{});
+    else if (cw <= 32)
+        go(std::integral_constant<int, 32>{});
+    else
+        go(std::integral_constant<int, 64>{});
+}
+
+// Marks 5 -> 6, link: (1) init forest, (2) window union, (3) cell and word
+// roots, (4) cell verify (listed or fused), then the deferred pairs.  The
+// per-cell kernels launch over the host's cell count (they also read the
+// count on the device and leave past it).
+template <typename T, int D, int M, typename K>
+void stage_link(Ctx& ctx, TrainArgs& a, GridTrain<T, K>& g) {
+    hipStream_t s = g.s;
+    const uint32_t R = g.R;
+    const uint64_t W = g.W;
+    g.par = ctx.arena.get<uint32_t>("parent", R);
+    g.gmin = ctx.arena.get<uint32_t>("gmin", R);
+    if (!R) return;
+    // (1) forest from the count pass's two smallest neighbours
+    uint32_t* wroot = ctx.arena.get<uint32_t>("word_root", W);
+    // (single device: the n-bit component-key map of rank_roots, zeroed here)
+    // (+ the root lists' counters after it, from a 128-B boundary)
+    const uint64_t NW = a.phase == 0 ? (g.n + 31) / 32 : 0;
+    const uint64_t NWz = NW ? ((NW + 31) & ~uint64_t(31)) + kRootLists * kRootCntStride : 0;
+    uint32_t* kbits = NW ? ctx.arena.get<uint32_t>("key_bits", NWz) : nullptr;
+    hipLaunchKernelGGL(init_kernel,
+                       dim3(sub_blocks(std::max<uint64_t>(std::max<uint64_t>(R, W), NWz), kInitSub)),
+                       dim3(kBlock), 0, s, R, g.core, g.mn, 1, g.par, g.gmin, wroot, W, kbits, NWz);
+    check_bounds(s, "init_kernel");
+    window_union<T, D, M>(ctx, g, g.Xs);   // (2)
+    const Cells C = g.cells();
+    const dim3 cgrid(blocks(g.ncells)), blk(kBlock);
+    uint32_t* croot = ctx.arena.get<uint32_t>("cell_root", R);
+    {   // (3) cell and word roots in one pass
+        uint32_t* big = ctx.arena.get<uint32_t>("big_cells", R / (kWordBig + 1) + 1);
+        uint32_t* mid = ctx.arena.get<uint32_t>("mid_cells", R / (kMidCell + 1) + 1);
+        uint32_t* nbig = g.ctrs + 8;   // [0] big, [1] mid (zeroed by the halo pass)
+        // (wroot starts at kNone: init_kernel)
+        const bool slots32 = W < 0xFFFFFFFFull;   // directory slots < 2^32 - 1
+        hipLaunchKernelGGL((slots32 ? cell_word_root_kernel<K, true> : cell_word_root_kernel<K, false>),
+                           cgrid, blk, 0, s, g.cstart, g.dncells, g.ckeys, g.par, croot, wroot, mid,
+                           nbig + 1, big, nbig, g.pages);
+        hipLaunchKernelGGL((mid_cell_word_root_kernel<K>), dim3(2048), blk, 0, s, g.cstart, g.ckeys,
+                           mid, nbig + 1, g.par, croot, wroot, g.pages);
+        hipLaunchKernelGGL((big_cell_word_root_kernel<K>), dim3(1024), blk, 0, s, g.cstart, g.ckeys,
+                           big, nbig, g.par, croot, wroot, g.pages);
+    }
+    const uint32_t pcap = (uint32_t)std::min<uint64_t>(R, 64ull << 20);
+    uint2* plist = ctx.arena.get<uint2>("pair_list", pcap);
+    uint32_t* pcount = g.ctrs + 10;   // (zeroed by the halo pass)
+    // (4) verify: screen every cell, then work on the flagged ones only
+    uint8_t* vflag = ctx.arena.get<uint8_t>("verify_flags", R);
+    uint32_t* vlist = ctx.arena.get<uint32_t>("verify_list", R);
+    auto [vcnt, voff] = tile_bufs(ctx, cgrid.x);
+    if (ctx.verify_fused) {
+        // one pass over every cell: the screen's test inline (no flags,
+        // no list, no scan, no host read of the flagged count)
+        hipLaunchKernelGGL((cell_verify_kernel<T, D, M, K>), cgrid, blk, 0, s, g.Xs, g.keys, nullptr,
+                           0u, croot, wroot, C, xsub_of(ctx), g.eps, g.eps2, g.slo, g.shi, g.par,
+                           plist, pcap, pcount, g.sst, g.dncells);
+    } else {
+        hipLaunchKernelGGL((verify_screen_kernel<D, K>), cgrid, blk, 0, s, g.keys, g.dncells, croot,
+                           wroot, C, xsub_of(ctx), vflag, vcnt);
+        const uint32_t NV = (uint32_t)tile_offsets(ctx, vcnt, cgrid.x, voff, s, true);
+        if (NV) {
+            hipLaunchKernelGGL(flag_list_kernel, cgrid, blk, 0, s, vflag, g.dncells, voff, vlist);
+            hipLaunchKernelGGL((cell_verify_kernel<T, D, M, K>), dim3(blocks(NV)), blk, 0, s, g.Xs,
+                               g.keys, vlist, NV, croot, wroot, C, xsub_of(ctx), g.eps, g.eps2, g.slo,
+                               g.shi, g.par, plist, pcap, pcount, g.sst, nullptr);
+        }
+    }
+    hipLaunchKernelGGL((pair_kernel<T, D, M>), dim3(std::min(blocks(pcap), 4096u)), blk, 0, s, g.Xs,
+                       plist, pcount, pcap, g.cstart, croot, g.eps, g.eps2, g.slo, g.shi, g.par);
+}
+
+// Marks 6 -> 7: the merge touches only the records of points in several
+// neighbourhoods.
+void stage_merge(const GridState& g) {
+    if (g.P <= 1 || !g.R) return;
+    const unsigned gb = std::min(blocks(g.R), 2048u);
+    hipLaunchKernelGGL(rep_kernel, dim3(gb), dim3(kBlock), 0, g.s, g.dup_list, g.ctrs, g.vals, g.par,
+                       g.rep);
+    hipLaunchKernelGGL(merge_kernel, dim3(gb), dim3(kBlock), 0, g.s, g.dup_list, g.ctrs, g.vals, g.rep,
+                       g.par);
+}
+
+// Marks 7 -> 8: component roots.  Single device: the component keys are
+// ranked here (labels); sharded: keys stay global ids (merge first).
+void stage_roots(Ctx& ctx, TrainArgs& a, const GridState& g) {
+    hipStream_t s = g.s;
+    const uint32_t R = g.R;
+    if (!R) return;
+    // (gmin starts at kNone: init_kernel)
+    const unsigned rb = sub_blocks(R, kRootSub);
+    const uint32_t seg = ((rb + kRootLists - 1) / kRootLists) * (uint32_t)(kRootSub * kBlock);
+    const uint64_t NW = a.phase == 0 ? (g.n + 31) / 32 : 0;
+    uint32_t* rlist = NW ? ctx.arena.get<uint32_t>("root_list", (size_t)seg * kRootLists) : nullptr;
+    // (the key map and the root lists' counters after it: sized and zeroed by init_kernel)
+    uint32_t* kbits = NW ? ctx.arena.get<uint32_t>("key_bits", 1) : nullptr;
+    uint32_t* rcnt = NW ? kbits + ((NW + 31) & ~uint64_t(31)) : nullptr;
+    hipLaunchKernelGGL(roots_kernel, dim3(rb), dim3(kBlock), 0, s, R, g.vals, a.gid, g.par, g.gmin,
+                       rlist, rcnt, seg, g.ctrs + 1, ctx.sweep_stats ? 1 : 0);
+    if (a.phase == 0) {
+        // rank the component keys on the device; the component count is
+        // read with the train's last copy back (finish)
+        uint32_t* kpre = ctx.arena.get<uint32_t>("key_pre", NW);
+        const unsigned gb = kRootLists * 16;
+        hipLaunchKernelGGL(root_mark_kernel, dim3(gb), dim3(kBlock), 0, s, rlist, rcnt, seg, g.gmin,
+                           kbits);
+        rocprim::transform_iterator<const uint32_t*, PopcOp, uint32_t> pc(kbits, PopcOp{});
+        exclusive_sum(ctx, "key_scan_tmp", pc, kpre, 0u, (size_t)NW, s);
+        hipLaunchKernelGGL(root_rank_kernel, dim3(gb), dim3(kBlock), 0, s, rlist, rcnt, seg, kbits,
+                           kpre, NW, g.gmin, g.ctrs + 1);
+    } else if (ctx.sweep_stats) {
+        uint32_t* h = (uint32_t*)pinned(ctx, sizeof(uint32_t) * 4);
+        PD_HIP(hipMemcpyAsync(h, g.ctrs + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        sync(s);
+        ctx.t.core_records = h[0];
+    }
+}
+
+// After mark 8: the state run_b (and a sharded train's second call) reads,
+// and the sharded train's export records.
+void publish(Ctx& ctx, TrainArgs& a, const GridState& g, void* Xs) {
     PhaseState& st = ctx.st;
-    st.R = R;
-    st.n = n;
-    st.G = Gtot;
-    st.P = P;
-    st.d = D;
-    st.dtype = std::is_same<T, float>::value ? 0 : 1;
-    st.metric = M;
+    st.R = g.R;
+    st.n = g.n;
+    st.G = g.Gtot;
+    st.P = g.P;
+    st.d = a.d;
+    st.dtype = a.dtype;   // (0 float32, 1 float64: the dispatch's)
+    st.metric = a.metric;
     st.min_samples = a.min_samples;
-    st.key_bits = key_bits;
+    st.key_bits = g.key_bits;
     st.eps = a.eps;
-    st.slo = slo;
-    st.shi = shi;
+    st.slo = g.slo;
+    st.shi = g.shi;
+    st.ncells = g.ncells;
+    st.n_roots = 0;   // single device: set by finish
     st.Xs = Xs;
-    st.parts = parts;
-    st.part_start = part_start;
-    st.dir = dir;
-    st.pages = pages;
-    st.cstart = cstart;
-    st.vals = vals;
-    st.core = core;
-    st.par = par;
-    st.gmin = gmin;
-    st.cnt_rec = cnt_rec;
-    st.mn = mn;
+    st.parts = g.parts;
+    st.part_start = g.part_start;
+    st.dir = g.dir;
+    st.pages = g.pages;
+    st.cstart = g.cstart;
+    st.vals = g.vals;
+    st.core = g.core;
+    st.par = g.par;
+    st.gmin = g.gmin;
+    st.cnt_rec = g.cnt_rec;
+    st.mn = g.mn;
     st.n_exports = 0;
-    if (a.phase == 1 && R && a.xr) {
-        uint32_t* elist = nullptr;
-        const uint32_t NE = select_records(ctx, "export_list", R, IsExport{core, vals, a.xr},
-                                           &elist, s);
+    if (a.phase == 1 && g.R && a.xr) {
+        // ordered compaction of the export records' ids (keeps the spatial
+        // order, so a wave's records stay neighbours); the count syncs
+        uint32_t* elist = ctx.arena.get<uint32_t>("export_list", g.R);
+        const uint32_t NE = (uint32_t)compact_ordered(
+            ctx, "sel_cmp", (uint64_t)g.R, IsExport{g.core, g.vals, a.xr}, elist, nullptr, g.s);
         st.exp_gid = ctx.arena.get<uint32_t>("exp_gid", NE + 1);
         st.exp_key = ctx.arena.get<uint32_t>("exp_key", NE + 1);
         if (NE)
-            hipLaunchKernelGGL(export_kernel, dim3(blocks(NE)), dim3(kBlock), 0, s, NE, elist, vals,
-                               par, gmin, a.gid, st.exp_gid, st.exp_key);
+            hipLaunchKernelGGL(export_kernel, dim3(blocks(NE)), dim3(kBlock), 0, g.s, NE, elist, g.vals,
+                               g.par, g.gmin, a.gid, st.exp_gid, st.exp_key);
         PD_HIP(hipGetLastError());
         st.n_exports = NE;
     }
     a.n_exports = st.n_exports;
     st.valid = true;
+}
+
+// Phase A: halo records, sort, cell directory, core counts, union-find,
+// component keys (marks 0..8).  Leaves its device state in ctx.st.
+template <typename T, int D, typename K, int M>
+void run_a(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t Gtot,
+           int key_bits, EvTimer& tm) {
+    // key_of accumulates cell indices in double (exact below 2^53 cells)
+    if (Gtot >= (1ull << 53)) throw Error(-5, "eps grid of 2^53 cells or more");
+    GridTrain<T, K> g;
+    g.s = a.stream;
+    g.n = (uint64_t)a.n;
+    g.P = a.P;
+    g.Gtot = Gtot;
+    g.key_bits = key_bits;
+    g.X = (const T*)a.X;
+    tm.mark();   // 0
+    stage_halo<T, D, K>(ctx, a, hparts, g);
+    tm.mark();   // 1
+    stage_sort<K>(ctx, g);
+    tm.mark();   // 2
+    stage_gather<T, D, K>(ctx, a, g);
+    tm.mark();   // 3
+    stage_cells<K>(ctx, a, g);
+    tm.mark();   // 4
+    stage_count<T, D, M>(ctx, a, g, g.Xs);
+    tm.mark();   // 5
+    stage_link<T, D, M, K>(ctx, a, g);
+    PD_HIP(hipGetLastError());
+    tm.mark();   // 6
+    stage_merge(g);
+    tm.mark();   // 7
+    stage_roots(ctx, a, g);
+    PD_HIP(hipGetLastError());
+    tm.mark();   // 8
+    publish(ctx, a, g, g.Xs);
 }
 
 
@@ -3363,8 +3393,7 @@ void run_b(Ctx& ctx, TrainArgs& a, EvTimer& tm) {
     if (R) {
         uint32_t* blist = ctx.arena.get<uint32_t>("border_list", R);
         const unsigned tiles = (unsigned)(((uint64_t)R + kOwnTile - 1) / kOwnTile);
-        uint32_t* tcnt = ctx.arena.get<uint32_t>("tile_cnt", (size_t)tiles + 1);
-        uint64_t* toff = ctx.arena.get<uint64_t>("tile_off", (size_t)tiles + 1);
+        auto [tcnt, toff] = tile_bufs(ctx, tiles);
         // bucketed: owner_kernel writes the (point, key) pairs in record order
         // instead of scattering key_out; the border sweep fills in its keys
         uint2* recs = bucketed ? ctx.arena.get<uint2>("lab_recs", R) : nullptr;
@@ -3375,51 +3404,45 @@ void run_b(Ctx& ctx, TrainArgs& a, EvTimer& tm) {
                            st.cnt_rec, (const uint2*)st.mn, core_mask,
                            bucketed ? nullptr : key_out, a.core, a.counts, tcnt, recs);
         const uint32_t NB = (uint32_t)tile_offsets(ctx, tcnt, tiles, toff, s, true);
-        if (NB)
+        if (NB) {
             hipLaunchKernelGGL(border_list_kernel, dim3(tiles), dim3(kBlock), 0, s, R, vals, core,
                                toff, blist);
-        if (NB)
-            launch_border<T, D, M>(s, Xs, NB, blist, C, eps, eps2, slo, shi, vals, par, gmin,
-                                   key_out, recs ? (uint32_t*)recs + 1 : nullptr);
-        if (local) {
+            hipLaunchKernelGGL((border4_kernel<T, D, M, kBorderWpe>), dim3(blocks(NB)), dim3(kBlock),
+                               0, s, Xs, NB, blist, C, eps, eps2, slo, shi, vals, par, gmin, key_out,
+                               recs ? (uint32_t*)recs + 1 : nullptr);
+        }
+        if (bucketed) {
+            // the (point, key) pairs into coarse buckets of 2^19 points: a
+            // bucket's 2 MB of key_out stays in one XCD's 4 MB L2 (C4 border:
+            // 2^20 29.2, 2^19 27.9, 2^18 29.5 ms)
             int kLabBits = 19;
             while (((n + (1ull << kLabBits) - 1) >> kLabBits) > (uint64_t)kLabMaxBk) ++kLabBits;
             const int nbk = (int)((n + (1ull << kLabBits) - 1) >> kLabBits);
-            const int sb = kLabBits - kLabBitsL;
-            if (nbk > kLabMaxBk || sb > 6) throw Error(-5, "label buckets: too many points");
+            const int sb = kLabBits - kLabBitsL;   // (local: sub-buckets per bucket, 2^sb)
+            if (nbk > kLabMaxBk || (local && sb > 6))
+                throw Error(-5, "label buckets: too many points");
             uint32_t* bcnt = ctx.arena.get<uint32_t>("lab_bcnt", (size_t)nbk);
             uint2* pairs = ctx.arena.get<uint2>("lab_pairs", (size_t)nbk << kLabBits);
-            const size_t nsub = (size_t)nbk << sb;   // >= nbkL
-            uint32_t* bcnt2 = ctx.arena.get<uint32_t>("lab_bcnt2", nsub);
-            uint2* pairs2 = ctx.arena.get<uint2>("lab_pairs2", (size_t)nbkL << kLabBitsL);
             PD_HIP(hipMemsetAsync(bcnt, 0, sizeof(uint32_t) * nbk, s));
-            PD_HIP(hipMemsetAsync(bcnt2, 0, sizeof(uint32_t) * nsub, s));
             const unsigned ltiles = (unsigned)(((uint64_t)R + kLabTile - 1) / kLabTile);
             hipLaunchKernelGGL((label_bucket_kernel<kLabPer, kLabMaxBk>), dim3(ltiles),
                                dim3(kLabBlock), 0, s, R, recs, kLabBits, nbk, bcnt, pairs);
-            constexpr uint32_t tile = kLabBlock * kLabPerL;
-            const uint32_t tpb = ((1u << kLabBits) + tile - 1) / tile;
-            hipLaunchKernelGGL(label_split_kernel, dim3((unsigned)nbk * tpb), dim3(kLabBlock), 0, s,
-                               pairs, bcnt, kLabBits, tpb, bcnt2, pairs2);
-            hipLaunchKernelGGL(label_local_kernel, dim3((unsigned)nbkL), dim3(kLabBlock), 0, s,
-                               pairs2, bcnt2, (uint64_t)n, a.labels, a.core);
-        } else if (bucketed) {
-            // buckets of 2^19 points: a bucket's 2 MB of key_out stays in one
-            // XCD's 4 MB L2 (C4 border: 2^20 29.2, 2^19 27.9, 2^18 29.5 ms)
-            int kLabBits = 19;
-            while (((n + (1ull << kLabBits) - 1) >> kLabBits) > (uint64_t)kLabMaxBk) ++kLabBits;
-            const int nbk = (int)((n + (1ull << kLabBits) - 1) >> kLabBits);
-            if (nbk > kLabMaxBk) throw Error(-5, "label buckets: too many points");
-            uint32_t* bcnt = ctx.arena.get<uint32_t>("lab_bcnt", (size_t)nbk);
-            uint2* pairs = ctx.arena.get<uint2>("lab_pairs", (size_t)nbk << kLabBits);
-            PD_HIP(hipMemsetAsync(bcnt, 0, sizeof(uint32_t) * nbk, s));
-            const unsigned ltiles = (unsigned)(((uint64_t)R + kLabTile - 1) / kLabTile);
-            hipLaunchKernelGGL((label_bucket_kernel<kLabPer, kLabMaxBk>), dim3(ltiles),
-                               dim3(kLabBlock), 0, s, R, recs,
-                               kLabBits, nbk, bcnt, pairs);
-            const unsigned bpb = (1u << kLabBits) / (kBlock * 8);
-            hipLaunchKernelGGL(label_scatter_kernel, dim3((unsigned)nbk * bpb), dim3(kBlock), 0, s,
-                               pairs, bcnt, kLabBits, nbk, bpb, key_out);
+            if (local) {
+                const size_t nsub = (size_t)nbk << sb;   // >= nbkL
+                uint32_t* bcnt2 = ctx.arena.get<uint32_t>("lab_bcnt2", nsub);
+                uint2* pairs2 = ctx.arena.get<uint2>("lab_pairs2", (size_t)nbkL << kLabBitsL);
+                PD_HIP(hipMemsetAsync(bcnt2, 0, sizeof(uint32_t) * nsub, s));
+                constexpr uint32_t tile = kLabBlock * kLabPerL;
+                const uint32_t tpb = ((1u << kLabBits) + tile - 1) / tile;
+                hipLaunchKernelGGL(label_split_kernel, dim3((unsigned)nbk * tpb), dim3(kLabBlock), 0,
+                                   s, pairs, bcnt, kLabBits, tpb, bcnt2, pairs2);
+                hipLaunchKernelGGL(label_local_kernel, dim3((unsigned)nbkL), dim3(kLabBlock), 0, s,
+                                   pairs2, bcnt2, (uint64_t)n, a.labels, a.core);
+            } else {
+                const unsigned bpb = (1u << kLabBits) / (kBlock * 8);
+                hipLaunchKernelGGL(label_scatter_kernel, dim3((unsigned)nbk * bpb), dim3(kBlock), 0,
+                                   s, pairs, bcnt, kLabBits, nbk, bpb, key_out);
+            }
         }
     }
     PD_HIP(hipGetLastError());
@@ -3452,23 +3475,20 @@ void run_b(Ctx& ctx, TrainArgs& a, EvTimer& tm) {
 void finish(Ctx& ctx, TrainArgs& a, EvTimer& tm) {
     hipStream_t s = a.stream;
     if (a.phase != 2) {
-        // cell count, and (single device) the component count and core
-        // records (roots_kernel's counters): one copy back, one sync
-        uint32_t* hnc = (uint32_t*)pinned(ctx, 4 * sizeof(uint32_t));
-        hnc[0] = hnc[1] = hnc[2] = 0;
-        if (ctx.st.R) {
-            PD_HIP(hipMemcpyAsync(hnc, ctx.arena.get<uint32_t>("ncells", 4), sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, s));
-            if (a.phase == 0)
-                PD_HIP(hipMemcpyAsync(hnc + 1, ctx.arena.get<uint32_t>("train_ctrs", kCtrs) + 1,
-                                      2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        }
+        // the cell count (the host's since the cells stage), and (single
+        // device) the component count and core records (roots_kernel's
+        // counters): one copy back, one sync
+        uint32_t* hc = (uint32_t*)pinned(ctx, 2 * sizeof(uint32_t));
+        hc[0] = hc[1] = 0;
+        if (ctx.st.R && a.phase == 0)
+            PD_HIP(hipMemcpyAsync(hc, ctx.arena.get<uint32_t>("train_ctrs", kCtrs) + 1,
+                                  2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         sync(s);
-        ctx.t.cells_n = hnc[0];
+        ctx.t.cells_n = ctx.st.ncells;
         if (a.phase == 0) {
-            ctx.st.n_roots = hnc[1];
-            a.n_clusters = hnc[1];
-            if (ctx.sweep_stats) ctx.t.core_records = hnc[2];
+            ctx.st.n_roots = hc[0];
+            a.n_clusters = hc[0];
+            if (ctx.sweep_stats) ctx.t.core_records = hc[1];
         }
         if (ctx.sweep_stats && ctx.st.R) {
             unsigned long long* hs = (unsigned long long*)pinned(ctx, 10 * sizeof(unsigned long long));
@@ -3506,53 +3526,37 @@ void finish(Ctx& ctx, TrainArgs& a, EvTimer& tm) {
     ctx.t.total = tm.span(0, 10);
 }
 
-template <typename T, int D, typename K, int M>
-void run(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& hparts, uint64_t Gtot,
-         int key_bits) {
-    EvTimer tm(ctx, a.stream);
-    run_a<T, D, K, M>(ctx, a, hparts, Gtot, key_bits, tm);
-    if (a.phase == 0) run_b<T, D, M>(ctx, a, tm);
-    finish(ctx, a, tm);
-}
-
-template <typename T, int D>
-void run_b_m(Ctx& ctx, TrainArgs& a) {
-    EvTimer tm(ctx, a.stream);
-    if (ctx.st.metric == 0)
-        run_b<T, D, 0>(ctx, a, tm);
+// f(T, D, M) with the runtime dtype, d and metric as tags (Tag<float|double>,
+// Int<1..4>, Int<0|1>), as dispatch in assign.hip does for the queries.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <typename X>
+struct Tag {
+    using type = X;
+};
+template <typename F>
+void dispatch(int dtype, int d, int metric, F&& f) {
+    auto by_d = [&](auto T, auto M) {
+        switch (d) {
+            case 1: f(T, Int<1>{}, M); break;
+            case 2: f(T, Int<2>{}, M); break;
+            case 3: f(T, Int<3>{}, M); break;
+            case 4: f(T, Int<4>{}, M); break;
+            default: throw Error(-5, "grid path supports d <= 4");
+        }
+    };
+    auto by_metric = [&](auto T) {
+        if (metric == 0)
+            by_d(T, Int<0>{});
+        else
+            by_d(T, Int<1>{});
+    };
+    if (dtype == 0)
+        by_metric(Tag<float>{});
+    else if (dtype == 1)
+        by_metric(Tag<double>{});
     else
-        run_b<T, D, 1>(ctx, a, tm);
-    finish(ctx, a, tm);
-}
-
-template <typename T>
-void run_b_d(Ctx& ctx, TrainArgs& a) {
-    switch (ctx.st.d) {
-        case 1: run_b_m<T, 1>(ctx, a); break;
-        case 2: run_b_m<T, 2>(ctx, a); break;
-        case 3: run_b_m<T, 3>(ctx, a); break;
-        case 4: run_b_m<T, 4>(ctx, a); break;
-        default: throw Error(-5, "grid path supports d <= 4");
-    }
-}
-
-template <typename T, int D, typename K>
-void run_m(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& p, uint64_t G, int kb) {
-    if (a.metric == 0)
-        run<T, D, K, 0>(ctx, a, p, G, kb);
-    else
-        run<T, D, K, 1>(ctx, a, p, G, kb);
-}
-
-template <typename T, typename K>
-void run_d(Ctx& ctx, TrainArgs& a, const std::vector<PartGrid>& p, uint64_t G, int kb) {
-    switch (a.d) {
-        case 1: run_m<T, 1, K>(ctx, a, p, G, kb); break;
-        case 2: run_m<T, 2, K>(ctx, a, p, G, kb); break;
-        case 3: run_m<T, 3, K>(ctx, a, p, G, kb); break;
-        case 4: run_m<T, 4, K>(ctx, a, p, G, kb); break;
-        default: throw Error(-5, "grid path supports d <= 4");
-    }
+        throw Error(-1, "dtype must be 0 (float32) or 1 (float64)");
 }
 
 }  // namespace
@@ -3594,12 +3598,7 @@ void rank_labels_async(Ctx& ctx, const uint32_t* key, uint64_t n, int32_t* label
     if (n) {
         hipLaunchKernelGGL(root_flag_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, key, n, core_bit,
                            rflag);
-        size_t tb = 0;
-        PD_HIP(rocprim::exclusive_scan(nullptr, tb, rflag, rnk, 0u, (size_t)n,
-                                       rocprim::plus<uint32_t>(), s));
-        void* tmp = ctx.arena.get<char>("scan_tmp", tb);
-        PD_HIP(rocprim::exclusive_scan(tmp, tb, rflag, rnk, 0u, (size_t)n,
-                                       rocprim::plus<uint32_t>(), s));
+        exclusive_sum(ctx, "scan_tmp", rflag, rnk, 0u, (size_t)n, s);
         hipLaunchKernelGGL(label_kernel, dim3(blocks(n)), dim3(kBlock), 0, s, key, rnk, rflag, n,
                            core_bit, labels, core_from_key, dncl);
     }
@@ -3620,12 +3619,12 @@ void train(Ctx& ctx, TrainArgs& a) {
         if (!st.valid) throw Error(-1, "pd_train_end without a matching pd_train_begin");
         if (a.n != (int64_t)st.n) throw Error(-1, "pd_train_end: n differs from pd_train_begin");
         if (!a.keys_out && a.n) throw Error(-1, "keys output is required");
-        if (a.n) {
-            if (st.dtype == 0)
-                run_b_d<float>(ctx, a);
-            else
-                run_b_d<double>(ctx, a);
-        }
+        if (a.n)
+            dispatch(st.dtype, st.d, st.metric, [&](auto T, auto D, auto M) {
+                EvTimer tm(ctx, a.stream);
+                run_b<typename decltype(T)::type, decltype(D)::value, decltype(M)::value>(ctx, a, tm);
+                finish(ctx, a, tm);
+            });
         st.valid = false;
         return;
     }
@@ -3779,19 +3778,17 @@ void train(Ctx& ctx, TrainArgs& a) {
     a.dir_paged = paged;
     int key_bits = 1;
     while (key_bits < 64 && ((G - (G ? 1 : 0)) >> key_bits)) ++key_bits;
-    if (a.dtype == 0) {
-        if (G < 0xFFFFFFFFull)
-            run_d<float, uint32_t>(ctx, a, parts, G, key_bits);
+    dispatch(a.dtype, d, a.metric, [&](auto T, auto D, auto M) {
+        using Tq = typename decltype(T)::type;
+        constexpr int Dv = decltype(D)::value, Mv = decltype(M)::value;
+        EvTimer tm(ctx, a.stream);
+        if (G < 0xFFFFFFFFull)   // the key width: cell keys below 2^32 - 1
+            run_a<Tq, Dv, uint32_t, Mv>(ctx, a, parts, G, key_bits, tm);
         else
-            run_d<float, uint64_t>(ctx, a, parts, G, key_bits);
-    } else if (a.dtype == 1) {
-        if (G < 0xFFFFFFFFull)
-            run_d<double, uint32_t>(ctx, a, parts, G, key_bits);
-        else
-            run_d<double, uint64_t>(ctx, a, parts, G, key_bits);
-    } else {
-        throw Error(-1, "dtype must be 0 (float32) or 1 (float64)");
-    }
+            run_a<Tq, Dv, uint64_t, Mv>(ctx, a, parts, G, key_bits, tm);
+        if (a.phase == 0) run_b<Tq, Dv, Mv>(ctx, a, tm);
+        finish(ctx, a, tm);
+    });
 }
 
 }  // namespace pd

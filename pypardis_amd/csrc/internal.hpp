@@ -68,7 +68,7 @@ struct PhaseState {
     int P = 0, d = 0, dtype = 0, metric = 0, min_samples = 0, key_bits = 0;
     double eps = 0;
     float slo = -1.0f, shi = 0.0f;
-    uint32_t ncells = 0;
+    uint32_t ncells = 0;         // occupied cells (the train's one host read; PD_T_CELLS_N)
     uint32_t n_exports = 0;
     uint32_t n_roots = 0;        // components on this device (single device: clusters)
     void* Xs = nullptr;

@@ -112,6 +112,8 @@ def test_super_eps_lattice_every_point_alone(native, d, m, stats, fused, dtype):
         lab, core, ncl, cnt = _cluster(native, X, EPS, 1)
         t = ctx.timings()
         assert ncl == n
+        # spacing 1.03 eps exceeds every cell width: no two points share a cell
+        assert int(t["cells_n"]) == n
         assert np.array_equal(cnt, ref[2]) and np.array_equal(core, ref[1])
         assert np.array_equal(lab, np.arange(n)) and np.array_equal(lab, ref[0])
         if stats:

@@ -1036,12 +1036,14 @@ def test_dir_layouts_equal(native, name):
     g = load_golden(name)
     ctx = native.context()
     P = int(g["max_partitions"])
+    cells_n = []
     for layout in (1, 0):
         ctx.set_option(native.PD_OPT_DIR_PAGED, layout)
         try:
             lab, core, ncl, cnt = _cluster(native, g["X"], float(g["eps"]),
                                            int(g["min_samples"]), _metric(g), full=True)
             t = ctx.timings()
+            cells_n.append(int(t["cells_n"]))
             m = DBSCAN(eps=float(g["eps"]), min_samples=int(g["min_samples"]), metric=_metric(g),
                        max_partitions=P if P > 0 else None).train(_dev(g["X"]))
         finally:
@@ -1051,6 +1053,7 @@ def test_dir_layouts_equal(native, name):
         assert np.array_equal(core, g["sk_core"])
         assert np.array_equal(lab, g["sk_labels"]) and ncl == int(g["sk_labels"].max()) + 1
         assert np.array_equal(m.labels_.cpu().numpy().astype(np.int64), g["sk_labels"])
+    assert cells_n[0] == cells_n[1] > 0, cells_n   # the layout does not move a cell
 
 
 @pytest.mark.parametrize("cfg,n", [("C4", 4_000_000), ("C2", 1_000_000), ("C1", 300_000)])
