@@ -8,7 +8,8 @@ from pypardis_amd import *  # noqa: F401,F403
 from pypardis_amd import (__version__, ClusterAggregator, default_value, BoundingBox,  # noqa: F401
                           median_search_split, mean_var_split, min_var_split, KDPartitioner,
                           dbscan_partition, map_cluster_id, DBSCAN, k_distances,
-                          radius_neighbors, kneighbors)
+                          radius_neighbors, kneighbors, mutual_reachability_forest,
+                          dbscan_labels, ReachabilityForest)
 from pypardis_amd import aggregator, geometry, partition  # noqa: F401
 from pypardis_amd import dbscan as _dbscan_mod
 

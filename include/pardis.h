@@ -632,6 +632,38 @@ int32_t pd_index_radius_count(pd_index* index, const void* Q, int32_t dtype, int
 int32_t pd_index_radius_fill(pd_index* index, const void* Q, int32_t dtype, int64_t m,
                              double radius, const int64_t* offsets, int32_t* ids, double* acc,
                              int64_t capacity, void* stream);
+/* Mutual-reachability forest: the single-linkage tree of HDBSCAN / DBSCAN* at
+ * every eps <= the index's eps at once.  On an index over ALL n rows built with
+ * labels[i] = i (d <= 4), with acc the train's accumulator, thr = fl(eps * eps)
+ * (cityblock: eps), cd = pd_index_kdist(k) of the rows themselves and
+ *   w(i, j) = max(acc(i, j), cd[i], cd[j]),
+ * G holds the pairs i < j with w <= thr (ties in; a row with cd = inf is
+ * isolated).  Under the strict order (w, u, v), u = min(i, j), v = max(i, j),
+ * the minimum spanning forest of G is unique: that forest is the result, so it
+ * is one defined edge list, bit-reproducible, whatever the order of the rows.
+ *   u, v (device, int32[capacity]), w (device, fp64[capacity]): the E = n -
+ *   (components of G) edges, ascending by (w, u, v), u < v: the merge order of
+ *   the dendrogram; the cut at any eps' <= eps is the prefix with w <= thr'.
+ *   cd (device, fp64[n]): the core accumulators, input order.
+ *   *n_edges_host = E; *rounds_host = Boruvka rounds run (both nullable).
+ * capacity >= n - 1 (PD_EINVAL otherwise).  k < 1: PD_EINVAL; k >
+ * PD_KDIST_MAX_K, n > 2^31 - 1, an index of d > 4: PD_EUNSUPPORTED; labels that
+ * are not the row numbers: PD_EINVAL.  The index stays usable after an error.
+ * One host read per round, at most ceil(log2 n) + 1 rounds.  Synchronises the
+ * stream. */
+int32_t pd_index_mreach_forest(pd_index* index, int32_t k, int32_t* u, int32_t* v, double* w,
+                               double* cd, int64_t capacity, int64_t* n_edges_host,
+                               int32_t* rounds_host, void* stream);
+/* Labels of a cut of a forest over n rows: the components of its first
+ * n_prefix edges (u, v: device int32), on the rows with member[i] != 0 (device
+ * uint8[n]), numbered by their smallest member row — the train's numbering —,
+ * -1 on every other row.  With member = (cd <= thr') and the prefix w <= thr'
+ * these are the labels of a train at eps' on its core rows (DBSCAN*: borders
+ * stay -1).  *n_clusters_host (nullable) = labels used.  An endpoint outside
+ * [0, n): PD_EINVAL.  Synchronises the stream. */
+int32_t pd_forest_labels(pd_ctx* ctx, int64_t n, const int32_t* u, const int32_t* v,
+                         int64_t n_prefix, const uint8_t* member, int32_t* labels,
+                         int64_t* n_clusters_host, void* stream);
 int32_t pd_index_destroy(pd_index* index);
 
 /* ---- RCCL collectives of the sharded train (one rank per device).  They

@@ -25,5 +25,8 @@ from .dbscan import (
     DBSCAN,
     k_distances,
     radius_neighbors,
-    kneighbors
+    kneighbors,
+    mutual_reachability_forest,
+    dbscan_labels,
+    ReachabilityForest
 )

@@ -63,7 +63,8 @@ EXPORTS = ["pd_abi_version", "pd_last_error", "pd_ctx_create", "pd_ctx_destroy",
            "pd_comm_self_check", "pd_comm_size", "pd_index_build", "pd_index_query",
            "pd_index_destroy", "pd_cluster_weighted", "pd_train_weighted",
            "pd_train_tree_weighted", "pd_index_kdist", "pd_index_radius_count",
-           "pd_index_radius_fill", "pd_index_kneighbors"]
+           "pd_index_radius_fill", "pd_index_kneighbors", "pd_index_mreach_forest",
+           "pd_forest_labels"]
 
 
 class PardisError(RuntimeError):
@@ -160,6 +161,8 @@ def load():
             "pd_index_kneighbors": ([P, P, I32, I64, I32, P, P, P], I32),
             "pd_index_radius_count": ([P, P, I32, I64, D, P, P, P], I32),
             "pd_index_radius_fill": ([P, P, I32, I64, D, P, P, P, I64, P], I32),
+            "pd_index_mreach_forest": ([P, I32, P, P, P, P, I64, P, P, P], I32),
+            "pd_forest_labels": ([P, I64, P, P, I64, P, P, P, P], I32),
             "pd_index_destroy": ([P], I32),
             "pd_cluster_weighted": ([P, P, I32, I64, I32, D, I32, I32, P, P, P, P, P], I32),
             "pd_train_weighted": ([P, P, I32, I64, I32, D, I32, I32, I32, P, P, P, P, P, P, P, P],
@@ -710,6 +713,31 @@ class Index:
         self.radius_fill(Q, radius, indptr, ids, acc)
         return indptr, ids, acc
 
+    def mreach_forest(self, k, capacity=None):
+        """-> (u, v, w, cd, rounds): the minimum spanning forest of the
+        mutual-reachability graph of the index's rows at its ``eps``, unique
+        under the order (w, u, v) (pd_index_mreach_forest; an ``over_rows``
+        index, d <= 4).  ``u``, ``v`` int32 and ``w`` float64 device tensors of
+        E edges ascending by (w, u, v), ``cd`` float64[n] the core accumulators
+        (``kdist(rows, k)``), ``rounds`` the Borůvka rounds run.  ``capacity``:
+        edges to allocate, default n - 1 (what the library asks for)."""
+        if self.ptr is None:
+            raise ValueError("the index was closed")
+        n = self.n_core
+        cap = max(n - 1, 0) if capacity is None else int(capacity)
+        u = torch.empty(max(cap, 0), dtype=torch.int32, device=self.device)
+        v = torch.empty(max(cap, 0), dtype=torch.int32, device=self.device)
+        w = torch.empty(max(cap, 0), dtype=torch.float64, device=self.device)
+        cd = torch.empty(n, dtype=torch.float64, device=self.device)
+        ne, rounds = np.zeros(1, np.int64), np.zeros(1, np.int32)
+        _check(load().pd_index_mreach_forest(self.ptr, int(k), u.data_ptr() if cap > 0 else None,
+                                             v.data_ptr() if cap > 0 else None,
+                                             w.data_ptr() if cap > 0 else None,
+                                             cd.data_ptr() if n else None, cap, ne.ctypes.data,
+                                             rounds.ctypes.data, _stream(self.device)))
+        e = int(ne[0])
+        return u[:e], v[:e], w[:e], cd, int(rounds[0])
+
     @classmethod
     def over_rows(cls, X, r_max, metric=PD_EUCLIDEAN, ctx=None):
         """The index over every row of ``X`` with ``eps = r_max`` whose labels
@@ -739,6 +767,36 @@ class Index:
             self.close()
         except Exception:
             pass
+
+
+def forest_labels(u, v, n_prefix, member, ctx=None):
+    """-> (labels, n_clusters): int32 device labels of the components of the
+    first ``n_prefix`` edges (``u``, ``v``: int32 device tensors) on the rows
+    with ``member`` (uint8 / bool device tensor, one entry per row) set,
+    numbered by smallest member row, -1 elsewhere (pd_forest_labels)."""
+    require_gpu()
+    if member.dtype == torch.bool:
+        member = member.view(torch.uint8)
+    if member.dtype != torch.uint8 or member.dim() != 1 or not member.is_cuda:
+        raise TypeError("member must be a uint8 / bool device vector")
+    if u.dtype != torch.int32 or v.dtype != torch.int32 or u.shape != v.shape or u.dim() != 1:
+        raise TypeError("u and v must be int32 vectors of one length")
+    if u.device != member.device or v.device != member.device:
+        raise ValueError("u, v and member must be on one device")
+    n_prefix = int(n_prefix)
+    if not 0 <= n_prefix <= u.shape[0]:
+        raise ValueError(f"n_prefix {n_prefix} is outside the {u.shape[0]} edges")
+    member, u, v = member.contiguous(), u.contiguous(), v.contiguous()
+    ctx = ctx or context(member.device.index)
+    n = member.shape[0]
+    labels = torch.empty(n, dtype=torch.int32, device=member.device)
+    ncl = np.zeros(1, np.int64)
+    _check(load().pd_forest_labels(ctx.ptr, n, u.data_ptr() if n_prefix else None,
+                                   v.data_ptr() if n_prefix else None, n_prefix,
+                                   member.data_ptr() if n else None,
+                                   labels.data_ptr() if n else None, ncl.ctypes.data,
+                                   _stream(member.device)))
+    return labels, int(ncl[0])
 
 
 # ------------------------------------------------------- sharded train stages

@@ -927,6 +927,31 @@ int32_t pd_index_radius_fill(pd_index* index, const void* Q, int32_t dtype, int6
     });
 }
 
+int32_t pd_index_mreach_forest(pd_index* index, int32_t k, int32_t* u, int32_t* v, double* w,
+                               double* cd, int64_t capacity, int64_t* n_edges_host,
+                               int32_t* rounds_host, void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_mreach_forest(index->ix, k, u, v, w, cd, capacity, n_edges_host, rounds_host,
+                            (hipStream_t)stream);
+    });
+}
+
+int32_t pd_forest_labels(pd_ctx* ctx, int64_t n, const int32_t* u, const int32_t* v,
+                         int64_t n_prefix, const uint8_t* member, int32_t* labels,
+                         int64_t* n_clusters_host, void* stream) {
+    return guard(ctx, [&] {
+        if (!ctx) throw Error(PD_EINVAL, "null context");
+        if (n < 0 || n > 0x7FFFFFFFll) throw Error(PD_EINVAL, "pd_forest_labels: n out of range");
+        if (n_prefix < 0 || (n_prefix && (!u || !v)) || (n && (!member || !labels)))
+            throw Error(PD_EINVAL, "pd_forest_labels: bad arrays");
+        const int64_t ncl =
+            forest_labels(ctx->c, n, u, v, n_prefix, member, labels, (hipStream_t)stream);
+        if (n_clusters_host) *n_clusters_host = ncl;
+    });
+}
+
 int32_t pd_index_destroy(pd_index* index) {
     if (!index) return PD_OK;
     int32_t rc = guard(nullptr, [&] { index_destroy(index->ix); });

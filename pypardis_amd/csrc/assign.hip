@@ -44,6 +44,11 @@
 // 64-bit scan of the counts and a fill pass that writes each hit's label —
 // and k-nearest queries (pd_index_kneighbors): the k-distance
 // walk / tiles with a list of (accumulator, label) pairs, written out in order.
+// Built with labels[i] = i it also yields the mutual-reachability forest
+// (pd_index_mreach_forest; d <= 4): Borůvka rounds in which every
+// record walks its rows for the lightest edge to a row of another component,
+// behind a per-cell component short cut (ccomp, the analogue of clab);
+// pd_forest_labels cuts such a forest into the train's labels.
 //
 // The four query kinds share one walk and one tile sweep; a
 // kernel is a prologue, a sink, one call and its write-out.  The layers:
@@ -71,7 +76,9 @@
 // in eight instantiations and the second 0.7 - 1.5 % of its speed (DESIGN.md
 // §15 has the figures).
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -79,6 +86,7 @@
 #include "compact.hpp"
 #include "internal.hpp"
 #include "pred.hpp"
+#include "uf.hpp"
 
 namespace pd {
 
@@ -371,7 +379,9 @@ struct Rows {
 // kernel and throws.  Off (the default) PD_OK is `true` and costs nothing.
 // Sites: 40 a query number from `order`; 41 the key prefix into `tab`; 42 a
 // row's record run (covers Xs and lab alike); 43 / 44 a tile's rows / labels;
-// 45 a query's pair of radius offsets; 46 a k-nearest output slot.
+// 45 a query's pair of radius offsets; 46 a k-nearest output slot; the forest
+// (DESIGN.md §16): 47 a record-order read (cd_rec, comp_rec, the bests); 48 a
+// component table (comp, par, best_w, best_uv: row numbers); 49 the edge append.
 #ifndef PD_CHECK_BOUNDS
 #define PD_CHECK_BOUNDS 0
 #endif
@@ -1288,6 +1298,334 @@ __global__ __launch_bounds__(kBlock) void radius_empty_kernel(const int64_t* __r
     row.close(nullptr, i, cap, tally);
 }
 
+// ------------------------------------------- mutual-reachability forest
+// The minimum spanning forest of the DBSCAN* graph at the index's eps
+// (DESIGN.md §16): edges i < j with w(i, j) = max(acc(i, j), cd[i], cd[j]) <=
+// thr, cd = kdist(k), under the strict order (w, u, v) — one defined edge list.
+// Borůvka: a round finds, for every row, the lightest edge to a row of another
+// component (foreign_min_kernel: the index's own walk, a lane per record), takes
+// the minimum per component (two atomicMin passes over the rows' bests), hooks
+// the components' choices together (uf.hpp) and renames.  Components are named
+// by their smallest row, in input order (comp) and in record order (comp_rec);
+// ccomp[e] is the component every record of cell e is in, -1 when they differ
+// (cell_label_kernel over comp_rec), and a cell in the lane's own component is
+// skipped without reading its records — what makes the later rounds cheap.
+
+// The index's records back as rows (stride D) in record order: the queries of
+// the k-distance pass and of every round.  owner[label] = the record, for
+// perm_check_kernel; tally[1]: labels that are no row number.
+template <typename T, int D>
+__global__ __launch_bounds__(kBlock) void rec_rows_kernel(const T* __restrict__ Xs,
+                                                          const int32_t* __restrict__ lab,
+                                                          uint64_t n, T* __restrict__ Q,
+                                                          int32_t* __restrict__ owner,
+                                                          unsigned long long* __restrict__ tally) {
+    constexpr int S = Stride<D>::v;
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+#pragma unroll
+    for (int j = 0; j < D; ++j) Q[r * D + j] = Xs[r * S + j];
+    const int32_t l = lab[r];
+    if (l < 0 || (uint64_t)l >= n)
+        atomicAdd(tally + 1, 1ull);
+    else
+        owner[l] = (int32_t)r;
+}
+
+// tally[1] += the records whose label another record holds too: with none, and
+// none out of range, the labels are a permutation of the row numbers (the
+// index was built with labels[i] = i).
+__global__ __launch_bounds__(kBlock) void perm_check_kernel(const int32_t* __restrict__ lab,
+                                                            const int32_t* __restrict__ owner,
+                                                            uint64_t n,
+                                                            unsigned long long* __restrict__ tally) {
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    const int32_t l = lab[r];
+    if (l >= 0 && (uint64_t)l < n && owner[l] != (int32_t)r) atomicAdd(tally + 1, 1ull);
+}
+
+// Core accumulators to input order; every row its own component.
+__global__ __launch_bounds__(kBlock) void forest_init_kernel(
+    const int32_t* __restrict__ lab, const double* __restrict__ cd_rec, uint64_t n,
+    double* __restrict__ cd, uint32_t* __restrict__ par, int32_t* __restrict__ comp,
+    int32_t* __restrict__ comp_rec) {
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    const int32_t i = lab[r];
+    if (!PD_OK((uint64_t)(uint32_t)i < n, 48, i)) return;
+    cd[i] = cd_rec[r];
+    par[i] = (uint32_t)i;
+    comp[i] = i;
+    comp_rec[r] = i;
+}
+
+// One round's sweep.  Lane -> record r (through `order`, as every query kernel;
+// Q holds the records' rows, so the query number IS the record).  A candidate j
+// weighs w = max(acc, cd_i, cd_rec[j]) >= max(acc, cd_i): cd_rec[j], comp_rec[j]
+// and lab[j] are read only once that lower bound does not pass the lane's best.
+// The best is the minimum under (w, row of j) among the rows of other
+// components — for a fixed i the order of (w, min(i, j), max(i, j)).  (inf, -1):
+// no foreign row within thr, or cd_i = inf.  tally[2] / [3] (stats != 0): cells
+// met / skipped by the short cut.
+template <typename T, int D, int M, typename K>
+__global__ __launch_bounds__(kBlock) void foreign_min_kernel(
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxView<T, K> v,
+    double thr, const double* __restrict__ cd_rec, const int32_t* __restrict__ comp_rec,
+    const int32_t* __restrict__ ccomp, double* __restrict__ bw, int32_t* __restrict__ bj,
+    unsigned long long* __restrict__ tally, int stats) {
+    const QueryAt<T, D> q(Q, m, order, v.g, tally, kBlock);
+    unsigned seen = 0, skipped = 0;
+    if (q.where != kPast && PD_OK(q.qi < v.nrec, 47, q.qi)) {
+        const uint32_t r = (uint32_t)q.qi;
+        const double cdi = cd_rec[r];
+        double best = INFINITY;
+        int32_t bestj = -1;
+        if (q.where == kInGrid && cdi <= thr) {
+            const int32_t ci = comp_rec[r];
+            auto offer = [&](double acc, uint32_t j) {
+                const double lo = acc > cdi ? acc : cdi;
+                if (!(acc <= thr && lo <= best)) return;
+                const double cdj = cd_rec[j];
+                const double w = lo > cdj ? lo : cdj;
+                if (!(w <= thr && w <= best)) return;
+                if (comp_rec[j] == ci) return;
+                const int32_t row = v.lab[j];
+                if (w < best || row < bestj) {
+                    best = w;
+                    bestj = row;
+                }
+            };
+            for_each_row<D>(v.g, q.c, [&](uint64_t klo, uint64_t khi) {
+                for (uint32_t e = first_cell(v, klo); e < v.ncells && (uint64_t)v.ckey[e] <= khi;
+                     ++e) {
+                    ++seen;
+                    if (ccomp && ccomp[e] == ci) {
+                        ++skipped;
+                        continue;
+                    }
+                    uint32_t j = v.cstart[e];
+                    const uint32_t j1 = v.cstart[e + 1];
+                    if (!PD_OK(j <= j1 && j1 <= v.nrec, 42, j1)) continue;
+                    for (; j + 4 <= j1; j += 4) {
+                        double acc4[4];
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) acc4[t] = rec_acc<T, D, M>(v.Xs, j + t, q.a);
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) offer(acc4[t], j + t);
+                    }
+                    for (; j < j1; ++j) offer(rec_acc<T, D, M>(v.Xs, j, q.a), j);
+                }
+            });
+        }
+        bw[r] = best;
+        bj[r] = bestj;
+    }
+    if (stats) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            seen += (unsigned)__shfl_xor((int)seen, o, 64);
+            skipped += (unsigned)__shfl_xor((int)skipped, o, 64);
+        }
+        if ((threadIdx.x & 63) == 0 && seen) {
+            atomicAdd(tally + 2, (unsigned long long)seen);
+            atomicAdd(tally + 3, (unsigned long long)skipped);
+        }
+    }
+}
+
+// atomicMin(table[key], val) for the wave's active lanes, reduced across the
+// wave first: the lanes that share the first active lane's key fold into one
+// atomic, four times over, and what is left goes alone.  In cell order the late
+// rounds' waves hold one or two components, so a component of 1e8 rows costs
+// about n / 64 atomics on its word, not n.  Every lane of the wave must call.
+__device__ __forceinline__ void wave_min_into(bool active, uint32_t key, unsigned long long val,
+                                              unsigned long long* __restrict__ table,
+                                              uint64_t nkeys) {
+    const int lane = (int)(threadIdx.x & 63);
+    for (int it = 0; it < 4; ++it) {
+        const unsigned long long mask = __ballot(active);
+        if (!mask) return;
+        const int leader = __ffsll((long long)mask) - 1;
+        const uint32_t k0 = (uint32_t)__shfl((int)key, leader, 64);
+        const bool mine = active && key == k0;
+        unsigned long long x = mine ? val : ~0ull;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long y = __shfl_xor(x, o, 64);
+            x = y < x ? y : x;
+        }
+        if (lane == leader && PD_OK(k0 < nkeys, 48, k0)) atomicMin(table + k0, x);
+        active = active && !mine;
+    }
+    if (active && PD_OK(key < nkeys, 48, key)) atomicMin(table + key, val);
+}
+
+// best_w[c] = the smallest w any row of component c found (the bits of a
+// non-negative double order as uint64; ~0: none).
+__global__ __launch_bounds__(kBlock) void comp_min_w_kernel(
+    const double* __restrict__ bw, const int32_t* __restrict__ bj,
+    const int32_t* __restrict__ comp_rec, uint64_t n, unsigned long long* __restrict__ best_w) {
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool have = r < n && bj[r] >= 0;
+    const uint32_t c = have ? (uint32_t)comp_rec[r] : 0u;
+    const unsigned long long bits = have ? (unsigned long long)__double_as_longlong(bw[r]) : ~0ull;
+    wave_min_into(have, c, bits, best_w, n);
+}
+
+// best_uv[c] = the smallest (u << 32 | v), u < v, among the rows of c whose w
+// is best_w[c]: with it the component's choice is its minimum under (w, u, v).
+__global__ __launch_bounds__(kBlock) void comp_min_uv_kernel(
+    const double* __restrict__ bw, const int32_t* __restrict__ bj,
+    const int32_t* __restrict__ comp_rec, const int32_t* __restrict__ lab, uint64_t n,
+    const unsigned long long* __restrict__ best_w, unsigned long long* __restrict__ best_uv) {
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool have = r < n && bj[r] >= 0;
+    const uint32_t c = have ? (uint32_t)comp_rec[r] : 0u;
+    unsigned long long uv = ~0ull;
+    if (have) {
+        have = PD_OK(c < n, 48, c) &&
+               (unsigned long long)__double_as_longlong(bw[r]) == best_w[c];
+        const uint32_t i = (uint32_t)lab[r], j = (uint32_t)bj[r];
+        uv = i < j ? ((unsigned long long)i << 32) | j : ((unsigned long long)j << 32) | i;
+    }
+    wave_min_into(have, c, uv, best_uv, n);
+}
+
+// Every component with a choice unites with the component at the other end of
+// it and appends the edge — once: when both ends chose the same edge, the
+// smaller component does.  comp, best_w and best_uv are this round's and only
+// read; the appends of a wave share one atomicAdd on the counter.
+__global__ __launch_bounds__(kBlock) void forest_hook_kernel(
+    const int32_t* __restrict__ comp, uint64_t n, const unsigned long long* __restrict__ best_w,
+    const unsigned long long* __restrict__ best_uv, uint32_t* __restrict__ par,
+    int32_t* __restrict__ eu, int32_t* __restrict__ ev, double* __restrict__ ew, uint64_t cap,
+    unsigned long long* __restrict__ counter) {
+    const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool emit = false;
+    unsigned long long uv = 0, wb = 0;
+    if (c < n && (uint32_t)comp[c] == (uint32_t)c && best_w[c] != ~0ull) {
+        wb = best_w[c];
+        uv = best_uv[c];
+        const uint32_t u = (uint32_t)(uv >> 32), v = (uint32_t)uv;
+        if (PD_OK(u < n && v < n, 48, uv)) {
+            const uint32_t cu = (uint32_t)comp[u];
+            const uint32_t c2 = cu == (uint32_t)c ? (uint32_t)comp[v] : cu;
+            if (PD_OK(c2 < n, 48, c2)) {
+                emit = !(best_w[c2] == wb && best_uv[c2] == uv && c2 < (uint32_t)c);
+                uf_unite(par, (uint32_t)c, c2);
+            }
+        }
+    }
+    const unsigned long long mask = __ballot(emit);
+    if (!mask) return;
+    const int lane = (int)(threadIdx.x & 63), leader = __ffsll((long long)mask) - 1;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
+    base = __shfl(base, leader, 64);
+    if (emit) {
+        const uint64_t slot = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+        if (PD_OK(slot < cap, 49, slot) && slot < cap) {
+            eu[slot] = (int32_t)(uv >> 32);
+            ev[slot] = (int32_t)(uint32_t)uv;
+            ew[slot] = __longlong_as_double((long long)wb);
+        }
+    }
+}
+
+// The new names: every row's root (the smallest row of its component).
+__global__ __launch_bounds__(kBlock) void comp_refresh_kernel(uint32_t* __restrict__ par,
+                                                              const int32_t* __restrict__ lab,
+                                                              uint64_t n, int32_t* __restrict__ comp,
+                                                              int32_t* __restrict__ comp_rec) {
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    const uint32_t i = (uint32_t)lab[r];
+    if (!PD_OK(i < n, 48, i)) return;
+    const int32_t c = (int32_t)uf_find(par, i);
+    comp[i] = c;
+    comp_rec[r] = c;
+}
+
+// The final order (w, u, v), least significant key first: (u << 32 | v) ...
+__global__ __launch_bounds__(kBlock) void edge_uv_key_kernel(const int32_t* __restrict__ eu,
+                                                             const int32_t* __restrict__ ev,
+                                                             uint64_t E, uint64_t* __restrict__ key,
+                                                             uint32_t* __restrict__ perm) {
+    const uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= E) return;
+    key[e] = ((uint64_t)(uint32_t)eu[e] << 32) | (uint32_t)ev[e];
+    perm[e] = (uint32_t)e;
+}
+
+// ... then, stably, the bits of w.
+__global__ __launch_bounds__(kBlock) void edge_w_key_kernel(const double* __restrict__ ew,
+                                                            const uint32_t* __restrict__ perm,
+                                                            uint64_t E, uint64_t* __restrict__ key) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= E) return;
+    const uint32_t e = perm[t];
+    key[t] = PD_OK(e < E, 49, e) ? (uint64_t)__double_as_longlong(ew[e]) : 0;
+}
+
+__global__ __launch_bounds__(kBlock) void edge_gather_kernel(
+    const int32_t* __restrict__ eu, const int32_t* __restrict__ ev, const double* __restrict__ ew,
+    const uint32_t* __restrict__ perm, uint64_t E, int32_t* __restrict__ u, int32_t* __restrict__ v,
+    double* __restrict__ w) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= E) return;
+    const uint32_t e = perm[t];
+    if (!PD_OK(e < E, 49, e)) return;
+    u[t] = eu[e];
+    v[t] = ev[e];
+    w[t] = ew[e];
+}
+
+// pd_forest_labels: the prefix's unions; tally[0]: endpoints that are no row.
+__global__ __launch_bounds__(kBlock) void prefix_unite_kernel(const int32_t* __restrict__ u,
+                                                              const int32_t* __restrict__ v,
+                                                              uint64_t np, uint64_t n,
+                                                              uint32_t* __restrict__ par,
+                                                              unsigned long long* __restrict__ tally) {
+    const uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= np) return;
+    const int32_t a = u[e], b = v[e];
+    if (a < 0 || b < 0 || (uint64_t)a >= n || (uint64_t)b >= n) {
+        atomicAdd(tally, 1ull);
+        return;
+    }
+    uf_unite(par, (uint32_t)a, (uint32_t)b);
+}
+
+__global__ __launch_bounds__(kBlock) void iota_none_kernel(uint32_t* __restrict__ par,
+                                                           uint32_t* __restrict__ first,
+                                                           uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    par[i] = (uint32_t)i;
+    first[i] = kNone;
+}
+
+// first[root] = the smallest member row of the component.
+__global__ __launch_bounds__(kBlock) void first_member_kernel(uint32_t* __restrict__ par,
+                                                              const uint8_t* __restrict__ member,
+                                                              uint64_t n,
+                                                              uint32_t* __restrict__ first) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || !member[i]) return;
+    atomicMin(first + uf_find(par, (uint32_t)i), (uint32_t)i);
+}
+
+// The train's cluster key: a member's component's smallest member, kNone else.
+__global__ __launch_bounds__(kBlock) void member_key_kernel(uint32_t* __restrict__ par,
+                                                            const uint8_t* __restrict__ member,
+                                                            const uint32_t* __restrict__ first,
+                                                            uint64_t n, uint32_t* __restrict__ key) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    key[i] = member[i] ? first[uf_find(par, (uint32_t)i)] : kNone;
+}
+
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 uint64_t read_u64(Ctx& w, const unsigned long long* dev, int count, unsigned long long* host_out,
@@ -1673,7 +2011,183 @@ void radius_pass(Index& ix, const void* Q, uint64_t m, const RadiusCall& rc, hip
         pass(Int<2>{});
 }
 
+// The forest's per-call switches, read like PD_INDEX_SORT_MIN.
+// PD_MREACH_CELL_SKIP=0 turns the cell short cut off (same result; the A/B of
+// tools/mreach_bench.py and the tests); PD_MREACH_TRACE=<file> appends one JSON
+// line per round: its wall time up to the host read, the edges it emitted, the
+// cells its lanes met and skipped.
+bool cell_skip() {
+    const char* e = std::getenv("PD_MREACH_CELL_SKIP");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
+struct Forest {
+    int32_t* u;
+    int32_t* v;
+    double* w;
+    double* cd;
+    int64_t edges = 0;
+    int rounds = 0;
+};
+
+template <typename T, int D, int M, typename K>
+void forest_run(Index& ix, int k, Forest& f, hipStream_t s) {
+    Ctx& w = ix.work;
+    const uint64_t n = ix.nc;
+    const dim3 gn(blocks(n)), bl(kBlock);
+    const double thr = threshold(ix);
+    // tally: [0] QueryAt's non-finite count (a record never is), [1] labels that
+    // are no row number, [2] / [3] cells met / skipped, [4] the edge counter
+    unsigned long long* tally = w.arena.get<unsigned long long>("mr_tally", 5);
+    PD_HIP(hipMemsetAsync(tally, 0, 5 * sizeof(unsigned long long), s));
+    T* Q = w.arena.get<T>("mr_q", n * D);
+    int32_t* bj = w.arena.get<int32_t>("mr_bj", n);   // first: each label's record
+    hipLaunchKernelGGL((rec_rows_kernel<T, D>), gn, bl, 0, s, (const T*)ix.Xs, ix.lab, n, Q, bj,
+                       tally);
+    hipLaunchKernelGGL(perm_check_kernel, gn, bl, 0, s, ix.lab, bj, n, tally);
+    PD_HIP(hipGetLastError());
+    double* cd_rec = w.arena.get<double>("mr_cd", n);
+    index_kdist(&ix, Q, ix.dtype, (int64_t)n, k, cd_rec, s);   // syncs
+    unsigned long long h[5];
+    read_u64(w, tally, 5, h, s);
+    if (h[1])
+        throw Error(-1, "pd_index_mreach_forest: the index's labels are not its row numbers "
+                        "(build it with labels[i] = i)");
+    uint32_t* par = w.arena.get<uint32_t>("mr_par", n);
+    int32_t* comp = w.arena.get<int32_t>("mr_comp", n);
+    int32_t* comp_rec = w.arena.get<int32_t>("mr_comp_rec", n);
+    int32_t* ccomp = cell_skip() ? w.arena.get<int32_t>("mr_ccomp", ix.ncells) : nullptr;
+    double* bw = w.arena.get<double>("mr_bw", n);
+    unsigned long long* best_w = w.arena.get<unsigned long long>("mr_best_w", n);
+    unsigned long long* best_uv = w.arena.get<unsigned long long>("mr_best_uv", n);
+    const uint64_t cap = n - 1;
+    int32_t* eu = w.arena.get<int32_t>("mr_eu", cap);
+    int32_t* ev = w.arena.get<int32_t>("mr_ev", cap);
+    double* ew = w.arena.get<double>("mr_ew", cap);
+    hipLaunchKernelGGL(forest_init_kernel, gn, bl, 0, s, ix.lab, cd_rec, n, f.cd, par, comp,
+                       comp_rec);
+    PD_HIP(hipGetLastError());
+    const uint32_t* order = query_order<T, D, K>(ix, Q, n, s);
+    const char* trace = std::getenv("PD_MREACH_TRACE");
+    FILE* tf = trace && *trace ? std::fopen(trace, "a") : nullptr;
+    uint64_t E = 0;
+    try {
+        while (E < cap) {
+            const auto t0 = std::chrono::steady_clock::now();
+            if (ccomp)
+                hipLaunchKernelGGL(cell_label_kernel, dim3(blocks(ix.ncells)), bl, 0, s, ix.cstart,
+                                   comp_rec, ix.ncells, ccomp);
+            if (tf) PD_HIP(hipMemsetAsync(tally + 2, 0, 2 * sizeof(unsigned long long), s));
+            launch(foreign_min_kernel<T, D, M, K>, "foreign_min_kernel", n, kBlock, 0, s,
+                   (const T*)Q, n, order, view_of<T, K>(ix), thr, (const double*)cd_rec,
+                   (const int32_t*)comp_rec, (const int32_t*)ccomp, bw, bj, tally, tf ? 1 : 0);
+            PD_HIP(hipMemsetAsync(best_w, 0xFF, sizeof(unsigned long long) * n, s));
+            PD_HIP(hipMemsetAsync(best_uv, 0xFF, sizeof(unsigned long long) * n, s));
+            hipLaunchKernelGGL(comp_min_w_kernel, gn, bl, 0, s, bw, bj, comp_rec, n, best_w);
+            hipLaunchKernelGGL(comp_min_uv_kernel, gn, bl, 0, s, bw, bj, comp_rec, ix.lab, n,
+                               best_w, best_uv);
+            hipLaunchKernelGGL(forest_hook_kernel, gn, bl, 0, s, comp, n, best_w, best_uv, par, eu,
+                               ev, ew, cap, tally + 4);
+            hipLaunchKernelGGL(comp_refresh_kernel, gn, bl, 0, s, par, ix.lab, n, comp, comp_rec);
+            PD_HIP(hipGetLastError());
+            check_bounds_ix(s, "pd_index_mreach_forest");
+            read_u64(w, tally, 5, h, s);   // the round's one host read
+            ++f.rounds;
+            const uint64_t got = h[4] - E;
+            if (tf) {
+                const double ms = std::chrono::duration<double, std::milli>(
+                                      std::chrono::steady_clock::now() - t0).count();
+                std::fprintf(tf,
+                             "{\"round\": %d, \"ms\": %.3f, \"edges\": %llu, \"cells\": %llu, "
+                             "\"cells_skipped\": %llu}\n",
+                             f.rounds, ms, (unsigned long long)got, h[2], h[3]);
+            }
+            if (h[4] > cap)
+                throw Error(-3, "pd_index_mreach_forest: more than n - 1 edges (a cycle)");
+            if (got == 0) break;
+            E = h[4];
+        }
+    } catch (...) {
+        if (tf) std::fclose(tf);
+        throw;
+    }
+    if (tf) std::fclose(tf);
+    f.edges = (int64_t)E;
+    if (E == 0) return;
+    // (w, u, v) ascending: two stable passes of the record sort
+    uint64_t* key = w.arena.get<uint64_t>("mr_key", E);
+    uint32_t* perm = w.arena.get<uint32_t>("mr_perm", E);
+    const dim3 ge(blocks(E));
+    hipLaunchKernelGGL(edge_uv_key_kernel, ge, bl, 0, s, eu, ev, E, key, perm);
+    int nb = 1;
+    while (nb < 32 && ((n - 1) >> nb)) ++nb;
+    sort_pairs_inplace(w, key, 8, perm, E, 32 + nb, s);
+    hipLaunchKernelGGL(edge_w_key_kernel, ge, bl, 0, s, ew, perm, E, key);
+    sort_pairs_inplace(w, key, 8, perm, E, 63, s);
+    hipLaunchKernelGGL(edge_gather_kernel, ge, bl, 0, s, eu, ev, ew, perm, E, f.u, f.v, f.w);
+    PD_HIP(hipGetLastError());
+    check_bounds_ix(s, "pd_index_mreach_forest");
+    sync(s);
+}
+
 }  // namespace
+
+void index_mreach_forest(Index* ix, int k, int32_t* u, int32_t* v, double* w, double* cd,
+                         int64_t capacity, int64_t* n_edges_host, int32_t* rounds_host,
+                         hipStream_t s) {
+    const char* who = "pd_index_mreach_forest";
+    if (n_edges_host) *n_edges_host = 0;
+    if (rounds_host) *rounds_host = 0;
+    if (k < 1) throw Error(-1, std::string(who) + ": k must be >= 1");
+    if (k > kKdistMaxK) throw Error(-5, std::string(who) + ": k must be <= PD_KDIST_MAX_K (64)");
+    if (ix->d > kMaxDim)
+        throw Error(-5, std::string(who) + ": d = " + std::to_string(ix->d) +
+                            " is not supported: the forest needs the cell grid of d <= 4");
+    const uint64_t n = ix->nc;
+    if (n > 0x7FFFFFFFull) throw Error(-5, std::string(who) + ": n must be <= 2^31 - 1");
+    if (capacity < 0 || (uint64_t)capacity + 1 < n)
+        throw Error(-1, std::string(who) + ": capacity must be >= n - 1");
+    if (n == 0) return;
+    if (!cd || (n > 1 && (!u || !v || !w))) throw Error(-1, std::string(who) + ": null output");
+    Forest f{u, v, w, cd};
+    dispatch(
+        *ix,
+        [&](auto T, auto D, auto M, auto K) {
+            forest_run<typename decltype(T)::type, decltype(D)::value, decltype(M)::value,
+                       typename decltype(K)::type>(*ix, k, f, s);
+        },
+        [&](auto, auto) { throw Error(-5, std::string(who) + ": d > 4"); });
+    if (n_edges_host) *n_edges_host = f.edges;
+    if (rounds_host) *rounds_host = f.rounds;
+}
+
+// Labels of the cut: the components of the first n_prefix edges, on the member
+// rows, numbered by smallest member row (rank_labels: the train's numbering).
+int64_t forest_labels(Ctx& ctx, int64_t n, const int32_t* u, const int32_t* v, int64_t n_prefix,
+                      const uint8_t* member, int32_t* labels, hipStream_t s) {
+    if (n == 0) return 0;
+    const uint64_t un = (uint64_t)n, np = (uint64_t)n_prefix;
+    const dim3 gn(blocks(un)), bl(kBlock);
+    uint32_t* par = ctx.arena.get<uint32_t>("fl_par", un);
+    uint32_t* first = ctx.arena.get<uint32_t>("fl_first", un);
+    uint32_t* key = ctx.arena.get<uint32_t>("fl_key", un);
+    unsigned long long* tally = ctx.arena.get<unsigned long long>("fl_tally", 1);
+    PD_HIP(hipMemsetAsync(tally, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(iota_none_kernel, gn, bl, 0, s, par, first, un);
+    if (np)
+        hipLaunchKernelGGL(prefix_unite_kernel, dim3(blocks(np)), bl, 0, s, u, v, np, un, par,
+                           tally);
+    hipLaunchKernelGGL(first_member_kernel, gn, bl, 0, s, par, member, un, first);
+    hipLaunchKernelGGL(member_key_kernel, gn, bl, 0, s, par, member, (const uint32_t*)first, un,
+                       key);
+    PD_HIP(hipGetLastError());
+    rank_labels_async(ctx, key, un, labels, s);
+    const int64_t ncl = rank_labels_count(ctx, s);   // syncs
+    unsigned long long bad = 0;
+    read_u64(ctx, tally, 1, &bad, s);
+    if (bad) throw Error(-1, "pd_forest_labels: an edge's endpoint is not a row number");
+    return ncl;
+}
 
 Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const uint8_t* core,
                    const int32_t* labels, double eps, int metric, hipStream_t s) {

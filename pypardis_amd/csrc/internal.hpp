@@ -371,6 +371,13 @@ void index_radius_count(Index* ix, const void* Q, int dtype, int64_t m, double r
 void index_radius_fill(Index* ix, const void* Q, int dtype, int64_t m, double radius,
                        const int64_t* offsets, int32_t* ids, double* acc, int64_t capacity,
                        hipStream_t s);
+// The minimum spanning forest of the mutual-reachability graph at the index's
+// eps (an index over all rows with labels[i] = i), and the labels of a cut of it.
+void index_mreach_forest(Index* ix, int k, int32_t* u, int32_t* v, double* w, double* cd,
+                         int64_t capacity, int64_t* n_edges_host, int32_t* rounds_host,
+                         hipStream_t s);
+int64_t forest_labels(Ctx& ctx, int64_t n, const int32_t* u, const int32_t* v, int64_t n_prefix,
+                      const uint8_t* member, int32_t* labels, hipStream_t s);
 void index_destroy(Index* ix);
 int index_device(const Index* ix);
 int64_t index_cores(const Index* ix);

@@ -513,6 +513,105 @@ def kneighbors(data, k, r_max, metric='euclidean', queries=None, return_distance
     return _kneighbors(X, q, k, r_max, metric, return_distance, squared)
 
 
+class ReachabilityForest(collections.namedtuple(
+        "ReachabilityForest", ["u", "v", "distances", "core_distances"])):
+    """What ``mutual_reachability_forest`` returns: the four device tensors,
+    and beside them what ``dbscan_labels`` needs to cut the forest: ``r_max``,
+    ``metric``, ``squared`` and the native accumulators (``accumulators``,
+    ``core_accumulators``: the distances before any square root)."""
+
+    def __new__(cls, u, v, acc, core_acc, r_max, metric, squared):
+        root = not squared and metric == _native.PD_EUCLIDEAN
+        self = super().__new__(cls, u, v, torch.sqrt(acc) if root else acc,
+                               torch.sqrt(core_acc) if root else core_acc)
+        self.accumulators = acc
+        self.core_accumulators = core_acc
+        self.r_max = float(r_max)
+        self.metric = metric
+        self.squared = bool(squared)
+        return self
+
+
+def _mreach_forest(X, k, r_max, metric, squared):
+    """The forest of the rows of ``X`` (a device tensor): the index over all
+    rows is built, asked once and closed."""
+    if X.shape[1] > 4:
+        raise ValueError(f"mutual_reachability_forest: d = {X.shape[1]} is not supported: the "
+                         "forest needs the cell grid of d <= 4")
+    try:
+        index = _native.Index.over_rows(X, r_max, metric)
+        try:
+            u, v, acc, cd, _ = index.mreach_forest(k)
+        finally:
+            index.close()
+    except _native.PardisError as e:
+        if e.code == _native.PD_EINVAL and "NaN" in str(e):   # sklearn's ValueError
+            raise ValueError(str(e)) from None
+        raise
+    return ReachabilityForest(u, v, acc, cd, r_max, metric, squared)
+
+
+def mutual_reachability_forest(data, min_samples, r_max, metric='euclidean', squared=False,
+                               device=None):
+    """
+    :param data: the points, in any form ``DBSCAN.train`` takes (d <= 4, fewer
+        than 2^31 of them)
+    :param min_samples: k of the core distance (1 <= k <= 64), the point itself
+        included, as in ``DBSCAN``
+    :param r_max: cap: the forest spans the DBSCAN* graph at ``eps = r_max``
+    :param metric: 'euclidean' or 'cityblock' (string or scipy callable)
+    :param squared: euclidean only: return the squared distances — the native,
+        bit-reproducible accumulator — instead of their square roots
+    :return: ``ReachabilityForest(u, v, distances, core_distances)`` of device
+        tensors: int32 ``u < v`` and float64 ``distances`` of the E edges,
+        ascending by (distance, u, v), and float64[n] ``core_distances``
+        (``k_distances(data, min_samples, r_max)``; ``inf``: fewer than
+        ``min_samples`` rows within ``r_max``)
+
+    The mutual-reachability distance of rows i and j is ``max(dist(i, j),
+    core(i), core(j))``.  The edges are the minimum spanning forest of the pairs
+    at which it is ``<= r_max`` — unique, because ties are broken by (u, v), so
+    the result is one defined list and does not depend on the order of the
+    rows beyond their numbers.  E = n minus the number of connected components
+    (isolated rows included).  The list is the single-linkage merge order of
+    HDBSCAN's hierarchy, and for every ``eps <= r_max`` its prefix with
+    ``distance <= eps`` is the clustering of ``DBSCAN(eps, min_samples)`` on
+    the core points: see ``dbscan_labels``.  Single device.
+    """
+    k, r_max = _check_kdist_args(min_samples, r_max)
+    metric = _native.metric_code(metric)
+    X = as_points(data, device).X
+    return _mreach_forest(X, k, r_max, metric, squared)
+
+
+def dbscan_labels(forest, eps, squared=False):
+    """
+    :param forest: a ``ReachabilityForest``
+    :param eps: the radius of the cut, ``<= forest.r_max``
+    :param squared: euclidean only: ``eps`` is the squared radius, the bound on
+        the accumulator itself
+    :return: device int32[n]: on the rows that are core at ``(eps,
+        min_samples)`` the ``labels_`` of ``DBSCAN(eps, min_samples).train``
+        — the components of the forest's edges within ``eps``, numbered by
+        smallest member row —, -1 on every other row (DBSCAN*: border points
+        are not attached; ``predict`` on the cut's cores gives them)
+    """
+    eps = float(eps)
+    euclid = forest.metric == _native.PD_EUCLIDEAN
+    if not (eps > 0) or not np.isfinite(eps):
+        raise ValueError(f"eps must be a finite value > 0, got {eps!r}")
+    cap = forest.r_max * forest.r_max if euclid else forest.r_max
+    t = eps if (squared or not euclid) else eps * eps
+    if t > cap:
+        raise ValueError(f"eps = {eps!r} exceeds the forest's r_max = {forest.r_max!r}: it holds "
+                         "only the edges within r_max")
+    acc, cd = forest.accumulators, forest.core_accumulators
+    bound = torch.tensor([t], dtype=torch.float64, device=acc.device)
+    n_prefix = int(torch.searchsorted(acc, bound, right=True)[0])
+    labels, _ = _native.forest_labels(forest.u, forest.v, n_prefix, cd <= t)
+    return labels
+
+
 class DBSCAN(object):
     """
     :eps: nearest neighbor radius
@@ -847,6 +946,37 @@ class DBSCAN(object):
         else:
             X = q = as_points(data, self.device).X
         return _kneighbors(X, q, k, r_max, metric, return_distance, squared)
+
+    def mutual_reachability_forest(self, data=None, min_samples=None, r_max=None, squared=False):
+        """
+        :param data: the points, in any form ``train`` takes; None: the
+            training points
+        :param min_samples: default the model's ``min_samples``
+        :param r_max: default ``eps``
+        :param squared: as the module-level ``mutual_reachability_forest``
+        :return: as ``mutual_reachability_forest(points, min_samples, r_max,
+            metric)``: ``ReachabilityForest(u, v, distances, core_distances)``
+
+        After a train, with the defaults, ``dbscan_labels(forest, eps)`` equals
+        ``labels_`` on the core rows and is -1 elsewhere, and every smaller
+        ``eps`` is another cut of the same forest, with no retrain.  Before any
+        train ``data`` is required.  After a ``group=`` train each rank holds
+        only its slice, so ``data=None`` raises; given ``data`` is answered on
+        its own.  The index is built and closed per call.
+        """
+        k, r_max = _check_kdist_args(self.min_samples if min_samples is None else min_samples,
+                                     self.eps if r_max is None else r_max)
+        metric = _native.metric_code(self.metric)
+        if data is None:
+            if self._group_trained:
+                raise ValueError("mutual_reachability_forest() after a group= train needs data: "
+                                 "each rank holds only its slice of the points")
+            if self._points is None:
+                raise ValueError("mutual_reachability_forest before train needs data")
+            X = self._points.X
+        else:
+            X = as_points(data, self.device).X
+        return _mreach_forest(X, k, r_max, metric, squared)
 
     def radius_neighbors(self, data=None, radius=None, return_distance=True, squared=False,
                          sort_results=False, count_only=False):
