@@ -9,7 +9,8 @@ from pypardis_amd import (__version__, ClusterAggregator, default_value, Boundin
                           median_search_split, mean_var_split, min_var_split, KDPartitioner,
                           dbscan_partition, map_cluster_id, DBSCAN, k_distances,
                           radius_neighbors, kneighbors, mutual_reachability_forest,
-                          dbscan_labels, ReachabilityForest)
+                          dbscan_labels, ReachabilityForest, condensed_tree, hdbscan_labels,
+                          hdbscan, CondensedTree)
 from pypardis_amd import aggregator, geometry, partition  # noqa: F401
 from pypardis_amd import dbscan as _dbscan_mod
 

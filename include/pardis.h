@@ -664,6 +664,67 @@ int32_t pd_index_mreach_forest(pd_index* index, int32_t k, int32_t* u, int32_t* 
 int32_t pd_forest_labels(pd_ctx* ctx, int64_t n, const int32_t* u, const int32_t* v,
                          int64_t n_prefix, const uint8_t* member, int32_t* labels,
                          int64_t* n_clusters_host, void* stream);
+/* HDBSCAN from such a forest: condensed tree, stabilities, selection, labels.
+ * The n_edges edges (u, v, w: device, ascending by (w, u, v) as
+ * pd_index_mreach_forest writes them) are the single-linkage merge order: edge
+ * e has rank e, dist(e) = sqrt(w[e]) when dist_is_sqrt (euclidean accumulators)
+ * else w[e], lambda(e) = 1 / dist(e) with IEEE sqrt and division.  Pairs beyond
+ * the forest's cap are infinitely far: its components hang under a virtual root
+ * at lambda = 0.  With m = min_cluster_size >= 2, walking the dendrogram down
+ * from a node of >= m rows: both children >= m rows is a true split (the
+ * cluster ends, two are born at lambda(e)); a child of < m rows falls out, each
+ * of its rows p leaving the cluster at lambda_p = lambda(e); both < m: the
+ * cluster dies.  Components of >= m rows are the top-level clusters, born at 0;
+ * the rows of smaller ones are noise.  Tied weights merge in (w, u, v) order,
+ * which defines the result (another implementation may order ties differently).
+ *
+ * pd_forest_condense.  Per row (device): point_cluster int32[n] the cluster the
+ * row falls out of (-1 noise), point_lambda fp64[n] its lambda_p (0 noise).
+ * Per cluster (HOST arrays of `capacity` entries, the first *n_clusters_host
+ * written): clusters are numbered leaves first, ascending by smallest row, then
+ * the clusters that split, ascending by the rank of their split, so parent[x] >
+ * x or -1 (top level); birth and death lambda (death: the split, or the last
+ * fall-out of a leaf); size = rows at birth; lambda_max = the largest of the
+ * cluster's own lambda_p and its split's lambda (== death); stability = sum
+ * over own rows of (lambda_p - birth) + [splits] * rows_at_split * (death -
+ * birth), every term rounded on its own; the sum's association order is fixed
+ * (rows ascending, pairwise within runs of 256, runs left to right), so it is
+ * bit-reproducible.  capacity = 2 * (n / m) always suffices; below the need:
+ * PD_EINVAL with *n_clusters_host = the need, the point arrays unspecified.
+ * *rounds_host: rounds of the small-subtree stage (<= m - 1, one host read
+ * each; PD_HDBSCAN_TRACE=<file> appends a JSON line per round).  stage_ms_host
+ * (nullable, 8 doubles): synchronised wall ms of checks, rounds, classify,
+ * blobs, host tree, locate, reductions, total.  PD_EINVAL: an endpoint outside
+ * [0, n), w not ascending (or NaN), a cycle, n_edges > n - 1, m < 2, and w[0]
+ * <= 0 — min_samples or more identical rows, lambda would be infinite:
+ * deduplicate, or weight the distinct rows.  The context stays usable.
+ *
+ * pd_condensed_select (host only): target[x] = the selected ancestor-or-self of
+ * cluster x, -1 none.  method 0, excess of mass: bottom-up a cluster is
+ * selected, its descendants deselected, when its stability >= the sum of its
+ * children's best values, else it passes that sum up; method 1: every leaf.
+ * A forest with exactly one top-level cluster: that cluster is selectable only
+ * with allow_single_cluster.
+ *
+ * pd_condensed_labels: labels int32[n] (device) of the selected cluster of each
+ * row's cluster, numbered by smallest member row, -1 none; probabilities
+ * fp64[n] (device) = min(lambda_p, lambda_max(S)) / lambda_max(S), 0 for noise.
+ * *n_selected_host = labels used.  Both device calls synchronise the stream. */
+int32_t pd_forest_condense(pd_ctx* ctx, int64_t n, int64_t n_edges, const int32_t* u,
+                           const int32_t* v, const double* w, int32_t dist_is_sqrt,
+                           int64_t min_cluster_size, int32_t* point_cluster, double* point_lambda,
+                           int64_t capacity, int32_t* parent_host, double* birth_host,
+                           double* death_host, int64_t* size_host, double* stability_host,
+                           double* lambda_max_host, int64_t* n_clusters_host, int32_t* rounds_host,
+                           double* stage_ms_host, void* stream);
+int32_t pd_condensed_select(int64_t n_clusters, const int32_t* parent_host,
+                            const double* stability_host, int32_t method,
+                            int32_t allow_single_cluster, int32_t* target_host);
+int32_t pd_condensed_labels(pd_ctx* ctx, int64_t n, int64_t n_clusters,
+                            const int32_t* point_cluster, const double* point_lambda,
+                            const int32_t* target_host, const double* lambda_max_host,
+                            int32_t* labels, double* probabilities, int64_t* n_selected_host,
+                            void* stream);
 int32_t pd_index_destroy(pd_index* index);
 
 /* ---- RCCL collectives of the sharded train (one rank per device).  They

@@ -28,5 +28,9 @@ from .dbscan import (
     kneighbors,
     mutual_reachability_forest,
     dbscan_labels,
-    ReachabilityForest
+    ReachabilityForest,
+    condensed_tree,
+    hdbscan_labels,
+    hdbscan,
+    CondensedTree
 )

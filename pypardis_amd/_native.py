@@ -64,7 +64,8 @@ EXPORTS = ["pd_abi_version", "pd_last_error", "pd_ctx_create", "pd_ctx_destroy",
            "pd_index_destroy", "pd_cluster_weighted", "pd_train_weighted",
            "pd_train_tree_weighted", "pd_index_kdist", "pd_index_radius_count",
            "pd_index_radius_fill", "pd_index_kneighbors", "pd_index_mreach_forest",
-           "pd_forest_labels"]
+           "pd_forest_labels", "pd_forest_condense", "pd_condensed_select",
+           "pd_condensed_labels"]
 
 
 class PardisError(RuntimeError):
@@ -163,6 +164,10 @@ def load():
             "pd_index_radius_fill": ([P, P, I32, I64, D, P, P, P, I64, P], I32),
             "pd_index_mreach_forest": ([P, I32, P, P, P, P, I64, P, P, P], I32),
             "pd_forest_labels": ([P, I64, P, P, I64, P, P, P, P], I32),
+            "pd_forest_condense": ([P, I64, I64, P, P, P, I32, I64, P, P, I64, P, P, P, P, P, P, P,
+                                    P, P, P], I32),
+            "pd_condensed_select": ([I64, P, P, I32, I32, P], I32),
+            "pd_condensed_labels": ([P, I64, I64, P, P, P, P, P, P, P, P], I32),
             "pd_index_destroy": ([P], I32),
             "pd_cluster_weighted": ([P, P, I32, I64, I32, D, I32, I32, P, P, P, P, P], I32),
             "pd_train_weighted": ([P, P, I32, I64, I32, D, I32, I32, I32, P, P, P, P, P, P, P, P],
@@ -797,6 +802,108 @@ def forest_labels(u, v, n_prefix, member, ctx=None):
                                    labels.data_ptr() if n else None, ncl.ctypes.data,
                                    _stream(member.device)))
     return labels, int(ncl[0])
+
+
+SELECT_METHODS = {"eom": 0, "leaf": 1}
+CONDENSE_STAGES = ["checks", "rounds", "classify", "blobs", "host_tree", "locate", "reductions",
+                   "total"]
+
+
+def forest_condense(n, u, v, w, dist_is_sqrt, min_cluster_size, capacity=None, timings=False,
+                    ctx=None):
+    """-> dict: the condensed tree of a forest over ``n`` rows at
+    ``min_cluster_size`` (pd_forest_condense).  ``u``, ``v`` int32 and ``w``
+    float64 device tensors, ascending by (w, u, v).  ``point_cluster`` (int32)
+    and ``point_lambda`` (float64) are device tensors of n; ``parent`` (int32),
+    ``birth``, ``death``, ``stability``, ``lambda_max`` (float64) and ``size``
+    (int64) are HOST numpy arrays of one entry per cluster; ``rounds`` the
+    small-subtree rounds run; ``stage_ms`` (with ``timings``) the synchronised
+    wall time per stage.  ``capacity``: clusters to allocate, default
+    2 * (n // min_cluster_size), which always suffices."""
+    require_gpu()
+    if u.dtype != torch.int32 or v.dtype != torch.int32 or w.dtype != torch.float64:
+        raise TypeError("u and v must be int32, w float64")
+    if not (u.dim() == v.dim() == w.dim() == 1 and u.shape == v.shape == w.shape):
+        raise TypeError("u, v and w must be vectors of one length")
+    if not (u.is_cuda and u.device == v.device == w.device):
+        raise ValueError("u, v and w must be on one device")
+    n, m = int(n), int(min_cluster_size)
+    u, v, w = u.contiguous(), v.contiguous(), w.contiguous()
+    dev = u.device
+    ctx = ctx or context(dev.index)
+    cap = 2 * (n // max(m, 1)) if capacity is None else int(capacity)
+    pc = torch.empty(n, dtype=torch.int32, device=dev)
+    pl = torch.empty(n, dtype=torch.float64, device=dev)
+    parent = np.zeros(max(cap, 0), np.int32)
+    size = np.zeros(max(cap, 0), np.int64)
+    birth, death, stab, lmax = (np.zeros(max(cap, 0), np.float64) for _ in range(4))
+    ncl, rounds = np.zeros(1, np.int64), np.zeros(1, np.int32)
+    ms = np.zeros(len(CONDENSE_STAGES), np.float64)
+    e = u.shape[0]
+    hp = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+    _check(load().pd_forest_condense(
+        ctx.ptr, n, e, u.data_ptr() if e else None, v.data_ptr() if e else None,
+        w.data_ptr() if e else None, 1 if dist_is_sqrt else 0, m, pc.data_ptr() if n else None,
+        pl.data_ptr() if n else None, cap, hp(parent), hp(birth), hp(death), hp(size), hp(stab),
+        hp(lmax), ncl.ctypes.data, rounds.ctypes.data, ms.ctypes.data if timings else None,
+        _stream(dev)))
+    c = int(ncl[0])
+    out = dict(point_cluster=pc, point_lambda=pl, parent=parent[:c], birth=birth[:c],
+               death=death[:c], size=size[:c], stability=stab[:c], lambda_max=lmax[:c],
+               rounds=int(rounds[0]))
+    if timings:
+        out["stage_ms"] = dict(zip(CONDENSE_STAGES, ms.tolist()))
+    return out
+
+
+def condensed_select(parent, stability, method="eom", allow_single_cluster=False):
+    """-> int32 numpy ``target``: per cluster its selected ancestor-or-self, -1
+    none (pd_condensed_select; host arrays in and out)."""
+    if method not in SELECT_METHODS:
+        raise ValueError(f"cluster_selection_method {method!r}: 'eom' or 'leaf'")
+    parent = np.ascontiguousarray(parent, np.int32)
+    stability = np.ascontiguousarray(stability, np.float64)
+    if parent.shape != stability.shape or parent.ndim != 1:
+        raise ValueError("parent and stability must be vectors of one length")
+    target = np.full(parent.shape[0], -1, np.int32)
+    c = parent.shape[0]
+    _check(load().pd_condensed_select(c, parent.ctypes.data if c else None,
+                                      stability.ctypes.data if c else None,
+                                      SELECT_METHODS[method], 1 if allow_single_cluster else 0,
+                                      target.ctypes.data if c else None))
+    return target
+
+
+def condensed_labels(point_cluster, point_lambda, target, lambda_max, ctx=None):
+    """-> (labels int32, probabilities float64, n_selected): device tensors of
+    the selected cluster of each row, numbered by smallest member row
+    (pd_condensed_labels).  ``target`` and ``lambda_max`` are host arrays."""
+    require_gpu()
+    if point_cluster.dtype != torch.int32 or point_lambda.dtype != torch.float64:
+        raise TypeError("point_cluster must be int32, point_lambda float64")
+    if point_cluster.shape != point_lambda.shape or point_cluster.dim() != 1:
+        raise TypeError("point_cluster and point_lambda must be vectors of one length")
+    if not point_cluster.is_cuda or point_cluster.device != point_lambda.device:
+        raise ValueError("point_cluster and point_lambda must be on one device")
+    target = np.ascontiguousarray(target, np.int32)
+    lambda_max = np.ascontiguousarray(lambda_max, np.float64)
+    if target.shape != lambda_max.shape or target.ndim != 1:
+        raise ValueError("target and lambda_max must be vectors of one length")
+    pc, pl = point_cluster.contiguous(), point_lambda.contiguous()
+    dev = pc.device
+    ctx = ctx or context(dev.index)
+    n, c = pc.shape[0], target.shape[0]
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    prob = torch.empty(n, dtype=torch.float64, device=dev)
+    nsel = np.zeros(1, np.int64)
+    _check(load().pd_condensed_labels(ctx.ptr, n, c, pc.data_ptr() if n else None,
+                                      pl.data_ptr() if n else None,
+                                      target.ctypes.data if c else None,
+                                      lambda_max.ctypes.data if c else None,
+                                      labels.data_ptr() if n else None,
+                                      prob.data_ptr() if n else None, nsel.ctypes.data,
+                                      _stream(dev)))
+    return labels, prob, int(nsel[0])
 
 
 # ------------------------------------------------------- sharded train stages

@@ -952,6 +952,88 @@ int32_t pd_forest_labels(pd_ctx* ctx, int64_t n, const int32_t* u, const int32_t
     });
 }
 
+int32_t pd_forest_condense(pd_ctx* ctx, int64_t n, int64_t n_edges, const int32_t* u,
+                           const int32_t* v, const double* w, int32_t dist_is_sqrt,
+                           int64_t min_cluster_size, int32_t* point_cluster, double* point_lambda,
+                           int64_t capacity, int32_t* parent_host, double* birth_host,
+                           double* death_host, int64_t* size_host, double* stability_host,
+                           double* lambda_max_host, int64_t* n_clusters_host, int32_t* rounds_host,
+                           double* stage_ms_host, void* stream) {
+    return guard(ctx, [&] {
+        const char* who = "pd_forest_condense";
+        if (n_clusters_host) *n_clusters_host = 0;
+        if (rounds_host) *rounds_host = 0;
+        if (!ctx) throw Error(PD_EINVAL, "null context");
+        if (n < 0 || n > 0x7FFFFFFFll)
+            throw Error(PD_EINVAL, std::string(who) + ": n out of range");
+        if (min_cluster_size < 2)
+            throw Error(PD_EINVAL, std::string(who) + ": min_cluster_size must be >= 2");
+        if (n_edges < 0 || n_edges > std::max<int64_t>(n - 1, 0))
+            throw Error(PD_EINVAL, std::string(who) + ": a forest over n rows has at most n - 1 "
+                                                      "edges");
+        if (n_edges && (!u || !v || !w)) throw Error(PD_EINVAL, std::string(who) + ": null edges");
+        if (n && (!point_cluster || !point_lambda))
+            throw Error(PD_EINVAL, std::string(who) + ": null point arrays");
+        if (capacity < 0 || (capacity && (!parent_host || !birth_host || !death_host ||
+                                          !size_host || !stability_host || !lambda_max_host)))
+            throw Error(PD_EINVAL, std::string(who) + ": bad cluster arrays");
+        Condensed o;
+        o.point_cluster = point_cluster;
+        o.point_lambda = point_lambda;
+        o.capacity = capacity;
+        o.parent = parent_host;
+        o.birth = birth_host;
+        o.death = death_host;
+        o.size = size_host;
+        o.stability = stability_host;
+        o.lambda_max = lambda_max_host;
+        o.stage_ms = stage_ms_host;
+        try {
+            forest_condense(ctx->c, n, n_edges, u, v, w, dist_is_sqrt != 0, min_cluster_size, o,
+                            (hipStream_t)stream);
+        } catch (...) {
+            if (n_clusters_host) *n_clusters_host = o.n_clusters;   // what capacity must hold
+            if (rounds_host) *rounds_host = o.rounds;
+            throw;
+        }
+        if (n_clusters_host) *n_clusters_host = o.n_clusters;
+        if (rounds_host) *rounds_host = o.rounds;
+    });
+}
+
+int32_t pd_condensed_select(int64_t n_clusters, const int32_t* parent_host,
+                            const double* stability_host, int32_t method,
+                            int32_t allow_single_cluster, int32_t* target_host) {
+    return guard(nullptr, [&] {
+        if (n_clusters < 0 || n_clusters > 0x7FFFFFFFll ||
+            (n_clusters && (!parent_host || !stability_host || !target_host)))
+            throw Error(PD_EINVAL, "pd_condensed_select: bad arrays");
+        condensed_select(n_clusters, parent_host, stability_host, method,
+                         allow_single_cluster != 0, target_host);
+    });
+}
+
+int32_t pd_condensed_labels(pd_ctx* ctx, int64_t n, int64_t n_clusters,
+                            const int32_t* point_cluster, const double* point_lambda,
+                            const int32_t* target_host, const double* lambda_max_host,
+                            int32_t* labels, double* probabilities, int64_t* n_selected_host,
+                            void* stream) {
+    return guard(ctx, [&] {
+        const char* who = "pd_condensed_labels";
+        if (n_selected_host) *n_selected_host = 0;
+        if (!ctx) throw Error(PD_EINVAL, "null context");
+        if (n < 0 || n > 0x7FFFFFFFll || n_clusters < 0 || n_clusters > 0x7FFFFFFFll)
+            throw Error(PD_EINVAL, std::string(who) + ": n or n_clusters out of range");
+        if ((n && (!point_cluster || !point_lambda || !labels || !probabilities)) ||
+            (n_clusters && (!target_host || !lambda_max_host)))
+            throw Error(PD_EINVAL, std::string(who) + ": bad arrays");
+        const int64_t ncl =
+            condensed_labels(ctx->c, n, n_clusters, point_cluster, point_lambda, target_host,
+                             lambda_max_host, labels, probabilities, (hipStream_t)stream);
+        if (n_selected_host) *n_selected_host = ncl;
+    });
+}
+
 int32_t pd_index_destroy(pd_index* index) {
     if (!index) return PD_OK;
     int32_t rc = guard(nullptr, [&] { index_destroy(index->ix); });

@@ -378,6 +378,32 @@ void index_mreach_forest(Index* ix, int k, int32_t* u, int32_t* v, double* w, do
                          hipStream_t s);
 int64_t forest_labels(Ctx& ctx, int64_t n, const int32_t* u, const int32_t* v, int64_t n_prefix,
                       const uint8_t* member, int32_t* labels, hipStream_t s);
+// HDBSCAN from such a forest (hdbscan.hip): the condensed tree
+// at min_cluster_size m with its stabilities, the selection over it (host), and
+// the labels and probabilities of a selection.  point_*: device, n; the
+// per-cluster arrays: host, `capacity` entries.
+struct Condensed {
+    int32_t* point_cluster = nullptr;
+    double* point_lambda = nullptr;
+    int64_t capacity = 0;
+    int32_t* parent = nullptr;
+    double* birth = nullptr;
+    double* death = nullptr;
+    int64_t* size = nullptr;
+    double* stability = nullptr;
+    double* lambda_max = nullptr;
+    int64_t n_clusters = 0;      // out
+    int32_t rounds = 0;          // out: stage-1 rounds
+    double* stage_ms = nullptr;  // host, 8 (nullable): wall ms per stage, synchronised
+};
+void forest_condense(Ctx& ctx, int64_t n, int64_t n_edges, const int32_t* u, const int32_t* v,
+                     const double* w, int root, int64_t m, Condensed& out, hipStream_t s);
+void condensed_select(int64_t n_clusters, const int32_t* parent, const double* stability,
+                      int method, int allow_single, int32_t* target);
+int64_t condensed_labels(Ctx& ctx, int64_t n, int64_t n_clusters, const int32_t* point_cluster,
+                         const double* point_lambda, const int32_t* target_host,
+                         const double* lambda_max_host, int32_t* labels, double* prob,
+                         hipStream_t s);
 void index_destroy(Index* ix);
 int index_device(const Index* ix);
 int64_t index_cores(const Index* ix);

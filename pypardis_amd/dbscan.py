@@ -612,6 +612,123 @@ def dbscan_labels(forest, eps, squared=False):
     return labels
 
 
+class CondensedTree(collections.namedtuple(
+        "CondensedTree", ["parent", "birth_lambda", "death_lambda", "size", "stability",
+                          "lambda_max", "point_cluster", "point_lambda"])):
+    """What ``condensed_tree`` returns.  The six per-cluster arrays are HOST
+    numpy arrays (at most 2 * (n // min_cluster_size) entries: the selection
+    runs over them on the host); ``point_cluster`` (int32, -1 noise) and
+    ``point_lambda`` (float64) are device tensors of one entry per row.
+    ``min_cluster_size`` and ``rounds`` (the small-subtree rounds run) ride
+    along as attributes."""
+
+    def __new__(cls, raw, min_cluster_size):
+        self = super().__new__(cls, raw["parent"], raw["birth"], raw["death"], raw["size"],
+                               raw["stability"], raw["lambda_max"], raw["point_cluster"],
+                               raw["point_lambda"])
+        self.min_cluster_size = int(min_cluster_size)
+        self.rounds = raw["rounds"]
+        self.stage_ms = raw.get("stage_ms")
+        return self
+
+
+def _check_min_cluster_size(m):
+    if int(m) != m or m < 2:
+        raise ValueError(f"min_cluster_size must be an integer >= 2, got {m!r}")
+    return int(m)
+
+
+def condensed_tree(forest, min_cluster_size, timings=False):
+    """
+    :param forest: a ``ReachabilityForest``
+    :param min_cluster_size: m >= 2: a side of a merge with fewer rows falls out
+        of its cluster instead of splitting it
+    :return: ``CondensedTree(parent, birth_lambda, death_lambda, size, stability,
+        lambda_max, point_cluster, point_lambda)``: HDBSCAN's condensed tree
+        with lambda = 1 / distance.  Clusters are numbered leaves first
+        (ascending by smallest row), then the clusters that split (in merge
+        order), so ``parent[x] > x``, or -1 for a top-level cluster: a
+        component of the forest with at least m rows, born at lambda 0.
+        ``point_cluster[p]`` is the cluster row p falls out of, at
+        ``point_lambda[p]``; -1 for noise.
+
+    The forest's edge order (distance, u, v) is the merge order, ties included,
+    so the tree is one defined, bit-reproducible result; another
+    implementation may break tied merges differently.  An edge of distance 0
+    (``min_samples`` or more identical rows) makes lambda infinite and raises
+    ``ValueError``: deduplicate the rows, or train on the distinct ones with
+    ``sample_weight``.  Single device.
+    """
+    m = _check_min_cluster_size(min_cluster_size)
+    n = forest.core_accumulators.shape[0]
+    try:
+        raw = _native.forest_condense(n, forest.u, forest.v, forest.accumulators,
+                                      forest.metric == _native.PD_EUCLIDEAN, m, timings=timings)
+    except _native.PardisError as e:
+        if e.code == _native.PD_EINVAL and "weight 0" in str(e):
+            raise ValueError(str(e)) from None
+        raise
+    return CondensedTree(raw, m)
+
+
+def hdbscan_labels(forest, min_cluster_size, cluster_selection_method='eom',
+                   allow_single_cluster=False, return_tree=False):
+    """
+    :param forest: a ``ReachabilityForest``
+    :param min_cluster_size: as ``condensed_tree``
+    :param cluster_selection_method: 'eom' (excess of mass: a cluster is kept
+        when its stability is at least the sum of its children's best) or
+        'leaf' (every leaf of the condensed tree)
+    :param allow_single_cluster: let the one top-level cluster of a connected
+        forest be selected (sklearn's rule); several top-level clusters are
+        ordinary candidates either way
+    :return: ``(labels, probabilities)``, with ``return_tree`` also the
+        ``CondensedTree``: device int32 labels, numbered by smallest member
+        row, -1 for noise, and float64 ``min(lambda_p, lambda_max(S)) /
+        lambda_max(S)``, 0 for noise
+    """
+    if cluster_selection_method not in _native.SELECT_METHODS:
+        raise ValueError(f"cluster_selection_method {cluster_selection_method!r}: 'eom' or 'leaf'")
+    tree = condensed_tree(forest, min_cluster_size)
+    target = _native.condensed_select(tree.parent, tree.stability, cluster_selection_method,
+                                      allow_single_cluster)
+    labels, prob, _ = _native.condensed_labels(tree.point_cluster, tree.point_lambda, target,
+                                               tree.lambda_max)
+    return (labels, prob, tree) if return_tree else (labels, prob)
+
+
+def _hdbscan(X, m, min_samples, r_max, metric, method, allow_single, return_tree):
+    m = _check_min_cluster_size(m)
+    if method not in _native.SELECT_METHODS:
+        raise ValueError(f"cluster_selection_method {method!r}: 'eom' or 'leaf'")
+    k = min(m, _native.KDIST_MAX_K) if min_samples is None else min_samples
+    k, r_max = _check_kdist_args(k, r_max)
+    forest = _mreach_forest(X, k, r_max, metric, True)
+    return hdbscan_labels(forest, m, method, allow_single, return_tree)
+
+
+def hdbscan(data, min_cluster_size, min_samples=None, r_max=None, metric='euclidean',
+            cluster_selection_method='eom', allow_single_cluster=False, return_tree=False,
+            device=None):
+    """
+    :param data: the points, in any form ``DBSCAN.train`` takes (d <= 4)
+    :param min_cluster_size: m >= 2
+    :param min_samples: k of the core distance, the point itself included;
+        default ``min_cluster_size``, capped at 64
+    :param r_max: required: the cap of the forest; pairs further apart count as
+        infinitely far, so each component of the DBSCAN* graph at ``r_max`` is
+        clustered on its own
+    :return: as ``hdbscan_labels``
+
+    ``mutual_reachability_forest`` and ``hdbscan_labels`` in one call.
+    """
+    if r_max is None:
+        raise ValueError("hdbscan needs r_max, the cap of the mutual-reachability forest")
+    X = as_points(data, device).X
+    return _hdbscan(X, min_cluster_size, min_samples, r_max, _native.metric_code(metric),
+                    cluster_selection_method, allow_single_cluster, return_tree)
+
+
 class DBSCAN(object):
     """
     :eps: nearest neighbor radius
@@ -977,6 +1094,35 @@ class DBSCAN(object):
         else:
             X = as_points(data, self.device).X
         return _mreach_forest(X, k, r_max, metric, squared)
+
+    def hdbscan(self, min_cluster_size, data=None, min_samples=None, r_max=None,
+                cluster_selection_method='eom', allow_single_cluster=False, return_tree=False):
+        """
+        :param min_cluster_size: m >= 2
+        :param data: the points, in any form ``train`` takes; None: the
+            training points
+        :param min_samples: default ``min_cluster_size``, capped at 64 (not the
+            model's: HDBSCAN's convention)
+        :param r_max: default ``eps``
+        :return: as the module-level ``hdbscan(points, min_cluster_size,
+            min_samples, r_max, metric, ...)``: ``(labels, probabilities)``,
+            with ``return_tree`` also the ``CondensedTree``
+
+        The rules for ``data`` are ``mutual_reachability_forest``'s: before any
+        train, and after a ``group=`` train, it is required.
+        """
+        metric = _native.metric_code(self.metric)
+        if data is None:
+            if self._group_trained:
+                raise ValueError("hdbscan() after a group= train needs data: each rank holds "
+                                 "only its slice of the points")
+            if self._points is None:
+                raise ValueError("hdbscan before train needs data")
+            X = self._points.X
+        else:
+            X = as_points(data, self.device).X
+        return _hdbscan(X, min_cluster_size, min_samples, self.eps if r_max is None else r_max,
+                        metric, cluster_selection_method, allow_single_cluster, return_tree)
 
     def radius_neighbors(self, data=None, radius=None, return_distance=True, squared=False,
                          sort_results=False, count_only=False):
