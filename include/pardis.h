@@ -654,6 +654,49 @@ int32_t pd_index_radius_fill(pd_index* index, const void* Q, int32_t dtype, int6
 int32_t pd_index_mreach_forest(pd_index* index, int32_t k, int32_t* u, int32_t* v, double* w,
                                double* cd, int64_t capacity, int64_t* n_edges_host,
                                int32_t* rounds_host, void* stream);
+/* sample_weight on the index (the train's rule, pd_*_weighted above): for rows
+ * that stand for several points — deduplicated data with its multiplicities.
+ * W_j = llrint(weight[j] * 2^20) as an unsigned integer; with T = min_samples *
+ * 2^20, the weighted core accumulator of a query q is
+ *   cdw(q) = the acc(q, j) at which the running sum of W_j, over the rows j
+ *            with acc(q, j) <= thr and W_j > 0 taken ascending by acc, first
+ *            reaches T; +inf when it never does
+ * (an integer sum: exact, and the same in any order; ties in acc do not matter).
+ * A query that is a row counts itself with its own weight; a row of weight 0
+ * adds nothing, also to itself, and still has a cdw.  So for any eps <= the
+ * index's eps a weighted train's core flag of row i is cdw[i] <= eps * eps
+ * (cityblock: <= eps) exactly; with unit weights cdw is pd_index_kdist(k) bit
+ * for bit; with integer multiplicities c >= 1 it is pd_index_kdist(k) of the
+ * rows repeated c times.
+ *
+ * pd_index_set_weights: weight (device, fp64[n]), one per row in input order,
+ * on an index over ALL n rows built with labels[i] = i (PD_EINVAL otherwise; n
+ * <= 2^31 - 1).  A weight that is not finite or outside [0, 2^31]: PD_EINVAL
+ * with "sample_weight" in the message; the index then has no weights but stays
+ * usable.  The weights are copied into the index (4 bytes per row, released with
+ * it); a second call replaces them.  One host read; synchronises the stream.
+ *
+ * pd_index_kdist_weighted: out[m] = cdw of each query, otherwise as
+ * pd_index_kdist (same arguments and errors; min_samples takes k's place).  An
+ * index without weights: PD_EINVAL.  Each query keeps a list of slots = ceil(T
+ * / W_min) candidates, W_min the smallest non-zero W (the slots smallest
+ * candidates always hold the crossing); slots > PD_KDIST_MAX_K (64):
+ * PD_EUNSUPPORTED — multiplicities >= 1 always fit, weights >= 0.5 up to
+ * min_samples 32.
+ *
+ * pd_index_mreach_forest_weighted: pd_index_mreach_forest with cd = cdw of the
+ * rows, w(i, j) = max(acc(i, j), cdw[i], cdw[j]); everything else — G, the order
+ * (w, u, v), the outputs, the errors — is unchanged, so pd_forest_labels with
+ * member = (cd <= thr') and the prefix w <= thr' gives the labels of a WEIGHTED
+ * train at eps' on its core rows.  Also PD_EINVAL without weights and
+ * PD_EUNSUPPORTED for slots > 64. */
+int32_t pd_index_set_weights(pd_index* index, const double* weight, void* stream);
+int32_t pd_index_kdist_weighted(pd_index* index, const void* Q, int32_t dtype, int64_t m,
+                                int32_t min_samples, double* out, void* stream);
+int32_t pd_index_mreach_forest_weighted(pd_index* index, int32_t min_samples, int32_t* u,
+                                        int32_t* v, double* w, double* cd, int64_t capacity,
+                                        int64_t* n_edges_host, int32_t* rounds_host,
+                                        void* stream);
 /* Labels of a cut of a forest over n rows: the components of its first
  * n_prefix edges (u, v: device int32), on the rows with member[i] != 0 (device
  * uint8[n]), numbered by their smallest member row — the train's numbering —,

@@ -65,7 +65,8 @@ EXPORTS = ["pd_abi_version", "pd_last_error", "pd_ctx_create", "pd_ctx_destroy",
            "pd_train_tree_weighted", "pd_index_kdist", "pd_index_radius_count",
            "pd_index_radius_fill", "pd_index_kneighbors", "pd_index_mreach_forest",
            "pd_forest_labels", "pd_forest_condense", "pd_condensed_select",
-           "pd_condensed_labels"]
+           "pd_condensed_labels", "pd_index_set_weights", "pd_index_kdist_weighted",
+           "pd_index_mreach_forest_weighted"]
 
 
 class PardisError(RuntimeError):
@@ -163,6 +164,9 @@ def load():
             "pd_index_radius_count": ([P, P, I32, I64, D, P, P, P], I32),
             "pd_index_radius_fill": ([P, P, I32, I64, D, P, P, P, I64, P], I32),
             "pd_index_mreach_forest": ([P, I32, P, P, P, P, I64, P, P, P], I32),
+            "pd_index_set_weights": ([P, P, P], I32),
+            "pd_index_kdist_weighted": ([P, P, I32, I64, I32, P, P], I32),
+            "pd_index_mreach_forest_weighted": ([P, I32, P, P, P, P, I64, P, P, P], I32),
             "pd_forest_labels": ([P, I64, P, P, I64, P, P, P, P], I32),
             "pd_forest_condense": ([P, I64, I64, P, P, P, I32, I64, P, P, I64, P, P, P, P, P, P, P,
                                     P, P, P], I32),
@@ -568,6 +572,7 @@ def train_tree(X, eps, min_samples, metric, ebox, tree, data_box=None, want_coun
 
 # ------------------------------------------------------------ assignment index
 PD_EINVAL = -1
+PD_EUNSUPPORTED = -5
 KDIST_MAX_K = 64   # PD_KDIST_MAX_K
 
 
@@ -637,6 +642,37 @@ class Index:
         out = torch.empty(m, dtype=torch.float64, device=Q.device)
         _check(load().pd_index_kdist(self.ptr, Q.data_ptr() if m else None, dt, m, int(k),
                                      out.data_ptr() if m else None, _stream(Q.device)))
+        return out
+
+    def set_weights(self, weight):
+        """Give the rows of an ``over_rows`` index their ``sample_weight``:
+        a contiguous float64 device tensor of one value per row, input order,
+        finite and in [0, 2**31] (pd_index_set_weights; the value check runs
+        on the device).  What ``kdist_weighted`` and ``mreach_forest(...,
+        weighted=True)`` read; a second call replaces the weights."""
+        if self.ptr is None:
+            raise ValueError("the index was closed")
+        w = weight
+        if not isinstance(w, torch.Tensor) or w.device != self.device:
+            raise TypeError("sample_weight must be a torch tensor on the index's device")
+        if w.dtype != torch.float64 or w.dim() != 1 or not w.is_contiguous():
+            raise TypeError("sample_weight must be a contiguous 1-D float64 tensor")
+        if w.shape[0] != self.n_core:
+            raise ValueError(f"sample_weight has {w.shape[0]} values for {self.n_core} rows")
+        _check(load().pd_index_set_weights(self.ptr, w.data_ptr() if w.shape[0] else None,
+                                           _stream(self.device)))
+
+    def kdist_weighted(self, Q, min_samples):
+        """float64 device tensor in the order of ``Q``: the accumulator at
+        which the weights of the index's rows, taken nearest first, reach
+        ``min_samples``; ``inf`` where those within its ``eps`` never do
+        (pd_index_kdist_weighted, after ``set_weights``)."""
+        dt = self._check_queries(Q)
+        m = Q.shape[0]
+        out = torch.empty(m, dtype=torch.float64, device=Q.device)
+        _check(load().pd_index_kdist_weighted(self.ptr, Q.data_ptr() if m else None, dt, m,
+                                              int(min_samples), out.data_ptr() if m else None,
+                                              _stream(Q.device)))
         return out
 
     def kneighbors(self, Q, k, return_acc=True):
@@ -718,14 +754,17 @@ class Index:
         self.radius_fill(Q, radius, indptr, ids, acc)
         return indptr, ids, acc
 
-    def mreach_forest(self, k, capacity=None):
+    def mreach_forest(self, k, capacity=None, weighted=False):
         """-> (u, v, w, cd, rounds): the minimum spanning forest of the
         mutual-reachability graph of the index's rows at its ``eps``, unique
         under the order (w, u, v) (pd_index_mreach_forest; an ``over_rows``
         index, d <= 4).  ``u``, ``v`` int32 and ``w`` float64 device tensors of
         E edges ascending by (w, u, v), ``cd`` float64[n] the core accumulators
         (``kdist(rows, k)``), ``rounds`` the Borůvka rounds run.  ``capacity``:
-        edges to allocate, default n - 1 (what the library asks for)."""
+        edges to allocate, default n - 1 (what the library asks for).
+        ``weighted``: the forest over the weighted core accumulators of
+        ``set_weights`` (pd_index_mreach_forest_weighted; ``cd`` is then
+        ``kdist_weighted(rows, k)``)."""
         if self.ptr is None:
             raise ValueError("the index was closed")
         n = self.n_core
@@ -735,11 +774,12 @@ class Index:
         w = torch.empty(max(cap, 0), dtype=torch.float64, device=self.device)
         cd = torch.empty(n, dtype=torch.float64, device=self.device)
         ne, rounds = np.zeros(1, np.int64), np.zeros(1, np.int32)
-        _check(load().pd_index_mreach_forest(self.ptr, int(k), u.data_ptr() if cap > 0 else None,
-                                             v.data_ptr() if cap > 0 else None,
-                                             w.data_ptr() if cap > 0 else None,
-                                             cd.data_ptr() if n else None, cap, ne.ctypes.data,
-                                             rounds.ctypes.data, _stream(self.device)))
+        call = load().pd_index_mreach_forest_weighted if weighted else \
+            load().pd_index_mreach_forest
+        _check(call(self.ptr, int(k), u.data_ptr() if cap > 0 else None,
+                    v.data_ptr() if cap > 0 else None, w.data_ptr() if cap > 0 else None,
+                    cd.data_ptr() if n else None, cap, ne.ctypes.data, rounds.ctypes.data,
+                    _stream(self.device)))
         e = int(ne[0])
         return u[:e], v[:e], w[:e], cd, int(rounds[0])
 

@@ -938,6 +938,36 @@ int32_t pd_index_mreach_forest(pd_index* index, int32_t k, int32_t* u, int32_t* 
     });
 }
 
+int32_t pd_index_set_weights(pd_index* index, const double* weight, void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_set_weights(index->ix, weight, (hipStream_t)stream);
+    });
+}
+
+int32_t pd_index_kdist_weighted(pd_index* index, const void* Q, int32_t dtype, int64_t m,
+                                int32_t min_samples, double* out, void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        if (m < 0 || (m && (!Q || !out))) throw Error(PD_EINVAL, "bad query arrays");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_kdist_weighted(index->ix, Q, dtype, m, min_samples, out, (hipStream_t)stream);
+    });
+}
+
+int32_t pd_index_mreach_forest_weighted(pd_index* index, int32_t min_samples, int32_t* u,
+                                        int32_t* v, double* w, double* cd, int64_t capacity,
+                                        int64_t* n_edges_host, int32_t* rounds_host,
+                                        void* stream) {
+    return guard(nullptr, [&] {
+        if (!index || !index->ix) throw Error(PD_EINVAL, "null index");
+        PD_HIP(hipSetDevice(index_device(index->ix)));
+        index_mreach_forest_weighted(index->ix, min_samples, u, v, w, cd, capacity, n_edges_host,
+                                     rounds_host, (hipStream_t)stream);
+    });
+}
+
 int32_t pd_forest_labels(pd_ctx* ctx, int64_t n, const int32_t* u, const int32_t* v,
                          int64_t n_prefix, const uint8_t* member, int32_t* labels,
                          int64_t* n_clusters_host, void* stream) {

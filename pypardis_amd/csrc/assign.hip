@@ -48,7 +48,12 @@
 // (pd_index_mreach_forest; d <= 4): Borůvka rounds in which every
 // record walks its rows for the lightest edge to a row of another component,
 // behind a per-cell component short cut (ccomp, the analogue of clab);
-// pd_forest_labels cuts such a forest into the train's labels.
+// pd_forest_labels cuts such a forest into the train's labels.  Given the
+// rows' sample_weight (pd_index_set_weights) the same index
+// answers the weighted core accumulator (pd_index_kdist_weighted: the walk /
+// tiles with a list of (accumulator, weight) pairs — WRegList, WLdsList — and
+// the crossing of the running weight sum taken after it) and builds the forest
+// on it (pd_index_mreach_forest_weighted).
 //
 // The four query kinds share one walk and one tile sweep; a
 // kernel is a prologue, a sink, one call and its write-out.  The layers:
@@ -115,6 +120,13 @@ struct Index {
     uint32_t* cstart = nullptr;
     int32_t* clab = nullptr;
     uint32_t* tab = nullptr;
+    // pd_index_set_weights: the rows' fixed-point weights in the
+    // index's own order, clamped to kWeightClamp; wmin: the smallest non-zero
+    // unclamped one (0: no row has weight)
+    uint64_t n_rows = 0;      // rows given to the build
+    uint32_t* wrec = nullptr;
+    uint64_t wmin = 0;
+    bool weighted = false;
 };
 
 namespace {
@@ -1626,6 +1638,240 @@ __global__ __launch_bounds__(kBlock) void member_key_kernel(uint32_t* __restrict
     key[i] = member[i] ? first[uf_find(par, (uint32_t)i)] : kNone;
 }
 
+// ------------------------------------------------------ weighted k-distance
+// cdw(q) = the accumulator at which the running sum of the fixed-point weights
+// W of the rows with acc <= thr and W > 0, taken ascending by acc, reaches
+// T = k * 2^20; +inf when it never does.  W is the train's
+// fixed point (engine.hip, weight_fix_kernel), so cdw <= thr' is the weighted
+// train's core flag at every thr' <= thr.  With W_min the smallest non-zero W,
+// the slots = ceil(T / W_min) smallest positive-weight candidates hold the
+// crossing (their weights sum to >= slots * W_min >= T), so a list of `slots`
+// (acc, weight) pairs per lane is exact, and tau = min(thr, slots-th smallest
+// so far) prunes as in the unweighted lists.  A weight above T crosses wherever
+// it stands, so the index keeps min(W, kWeightClamp) — 32 bits —, kWeightClamp
+// = PD_KDIST_MAX_K * 2^20 >= every T; the running sum is taken in 64 bits.
+
+constexpr int kWeightBits = 20;
+constexpr double kWeightLimit = 2147483648.0;
+constexpr uint32_t kWeightClamp = (uint32_t)kKdistMaxK << kWeightBits;
+
+// The train's rule on the index's side: W = llrint(w * 2^20), valid when finite
+// and 0 <= w <= 2^31, else counted in stats[0] and stored as 0; stats[2] = the
+// smallest non-zero W (starts at ~0), one atomic per wave.
+__global__ __launch_bounds__(kBlock) void index_weight_fix_kernel(
+    const double* __restrict__ w, uint64_t n, uint64_t* __restrict__ W,
+    unsigned long long* __restrict__ stats) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const double x = i < n ? w[i] : 0.0;
+    const bool ok = x >= 0.0 && x <= kWeightLimit;   // (NaN fails both)
+    const uint64_t Wi = ok ? (uint64_t)llrint(x * (double)(1ull << kWeightBits)) : 0ull;
+    if (i < n) W[i] = Wi;
+    const unsigned long long b = __ballot(!ok);
+    const int lane = (int)(threadIdx.x & 63);
+    if (b && lane == __ffsll((long long)b) - 1) atomicAdd(stats, (unsigned long long)__popcll(b));
+    unsigned long long mn = Wi ? (unsigned long long)Wi : ~0ull;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long y = __shfl_xor(mn, o, 64);
+        mn = y < mn ? y : mn;
+    }
+    if (lane == 0 && mn != ~0ull) atomicMin(stats + 2, mn);
+}
+
+// wrec[r] = min(W[lab[r]], kWeightClamp): the weights in the index's own order
+// (d <= 4: records; d > 4: the compacted rows).  owner[label] = r for
+// perm_check_kernel; stats[1]: labels that are no row number.
+__global__ __launch_bounds__(kBlock) void index_weight_gather_kernel(
+    const uint64_t* __restrict__ W, const int32_t* __restrict__ lab, uint64_t n,
+    uint32_t* __restrict__ wrec, int32_t* __restrict__ owner,
+    unsigned long long* __restrict__ stats) {
+    const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    const int32_t l = lab[r];
+    if (l < 0 || (uint64_t)l >= n) {
+        atomicAdd(stats + 1, 1ull);
+        wrec[r] = 0u;
+        return;
+    }
+    owner[l] = (int32_t)r;
+    const uint64_t Wl = W[l];
+    wrec[r] = Wl > (uint64_t)kWeightClamp ? kWeightClamp : (uint32_t)Wl;
+}
+
+// RegList with the weight beside each accumulator: KT pairs kept ascending by
+// acc.  Slot s keeps its pair when that is <= the candidate and else takes the
+// larger of the candidate and slot s - 1's pair (an equal accumulator goes
+// behind its twins: every pair is kept once, whatever the ties) — 4 KT selects,
+// every index a compile-time constant.  The KT - slots padding slots hold
+// (-inf, 0), which no insert moves and which add nothing to the sum; empty
+// slots hold (+inf, 0).  The candidate's weight is read only once acc has
+// passed tau, and a zero weight is dropped there.
+template <int KT>
+struct WRegList {
+    double b[KT];
+    uint32_t wt[KT];
+    double thr;
+    const uint32_t* wsrc;   // wsrc[j]: candidate j's weight
+    __device__ __forceinline__ void init(const uint32_t* wsrc_, int slots, double thr_) {
+        wsrc = wsrc_;
+        thr = thr_;
+#pragma unroll
+        for (int s = 0; s < KT; ++s) {
+            b[s] = s < KT - slots ? -INFINITY : INFINITY;
+            wt[s] = 0u;
+        }
+    }
+    __device__ __forceinline__ double tau() const { return thr < b[KT - 1] ? thr : b[KT - 1]; }
+    __device__ __forceinline__ void offer(double acc, uint32_t j) {
+        // a tie with a full list's last slot changes no crossing
+        if (!(acc <= thr && acc < b[KT - 1])) return;
+        const uint32_t wa = wsrc[j];
+        if (wa == 0u) return;
+#pragma unroll
+        for (int s = KT - 1; s >= 1; --s) {
+            const bool stay = b[s] <= acc, up = b[s - 1] > acc;
+            const double hb = up ? b[s - 1] : acc;
+            const uint32_t hw = up ? wt[s - 1] : wa;
+            b[s] = stay ? b[s] : hb;
+            wt[s] = stay ? wt[s] : hw;
+        }
+        const bool stay = b[0] <= acc;
+        b[0] = stay ? b[0] : acc;
+        wt[0] = stay ? wt[0] : wa;
+    }
+    // the accumulator at which the running sum reaches `target`
+    __device__ __forceinline__ double result(uint32_t target) const {
+        unsigned long long sum = 0;
+        double r = INFINITY;
+        bool done = false;
+#pragma unroll
+        for (int s = 0; s < KT; ++s) {
+            sum += wt[s];
+            const bool hit = !done && sum >= (unsigned long long)target;
+            r = hit ? b[s] : r;
+            done = done || hit;
+        }
+        return r;
+    }
+};
+
+// LdsList with the weights in a second slot-major array (12 bytes per slot):
+// unordered, the largest accumulator's value and slot in registers.  The
+// crossing is taken once, after the walk: the smallest entry whose own and
+// smaller entries' weights sum to the target (k^2 reads per lane).
+struct WLdsList {
+    double* my;       // this lane's slot 0
+    uint32_t* myw;
+    int stride;       // lanes per block
+    int k, cnt, imax;
+    double thr, top;  // top: largest accumulator so far
+    const uint32_t* wsrc;   // wsrc[j]: candidate j's weight
+    __device__ __forceinline__ void init(const uint32_t* wsrc_, double* base, uint32_t* wbase,
+                                         int lane, int lanes, int k_, double thr_) {
+        wsrc = wsrc_;
+        my = base + lane;
+        myw = wbase + lane;
+        stride = lanes;
+        k = k_;
+        cnt = 0;
+        imax = 0;
+        thr = thr_;
+        top = -INFINITY;
+    }
+    __device__ __forceinline__ double tau() const { return cnt < k ? thr : top; }
+    __device__ __forceinline__ void offer(double acc, uint32_t j) {
+        if (cnt < k) {
+            if (!(acc <= thr)) return;
+            const uint32_t wa = wsrc[j];
+            if (wa == 0u) return;
+            my[(size_t)cnt * stride] = acc;
+            myw[(size_t)cnt * stride] = wa;
+            if (acc >= top) {
+                top = acc;
+                imax = cnt;
+            }
+            ++cnt;
+        } else if (acc < top) {
+            const uint32_t wa = wsrc[j];
+            if (wa == 0u) return;
+            my[(size_t)imax * stride] = acc;
+            myw[(size_t)imax * stride] = wa;
+            top = -INFINITY;
+            for (int s = 0; s < k; ++s) {
+                const double v = my[(size_t)s * stride];
+                if (v > top) {
+                    top = v;
+                    imax = s;
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ double result(uint32_t target) const {
+        double r = INFINITY;
+        for (int s = 0; s < cnt; ++s) {
+            const double as = my[(size_t)s * stride];
+            if (!(as < r)) continue;
+            unsigned long long sum = 0;
+            for (int t = 0; t < cnt; ++t)
+                sum += my[(size_t)t * stride] <= as ? myw[(size_t)t * stride] : 0u;
+            if (sum >= (unsigned long long)target) r = as;
+        }
+        return r;
+    }
+};
+
+// d <= 4: the shared walk into a weighted list; wrec[j] is record j's weight.
+// KT > 0: the list in registers (slots <= KT); KT == 0: in dynamic LDS,
+// slots * blockDim.x doubles and as many uint32.
+template <typename T, int D, int M, typename K, int KT>
+__global__ __launch_bounds__(kBlock) void wkdist_kernel(
+    const T* __restrict__ Q, uint64_t m, const uint32_t* __restrict__ order, IxView<T, K> v,
+    const uint32_t* __restrict__ wrec, double thr, int slots, uint32_t target,
+    double* __restrict__ out, unsigned long long* __restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const QueryAt<T, D> q(Q, m, order, v.g, bad, blockDim.x);
+    if (q.where == kPast) return;
+    if (q.where != kInGrid) {
+        out[q.qi] = INFINITY;
+        return;
+    }
+    typename std::conditional<(KT > 0), WRegList<(KT > 0 ? KT : 1)>, WLdsList>::type list;
+    if constexpr (KT > 0) {
+        list.init(wrec, slots, thr);
+    } else {
+        double* Bs = reinterpret_cast<double*>(smem);
+        list.init(wrec, Bs, reinterpret_cast<uint32_t*>(Bs + (size_t)slots * blockDim.x),
+                  (int)threadIdx.x, (int)blockDim.x, slots, thr);
+    }
+    walk<T, D, M>(v, q, list);
+    out[q.qi] = list.result(target);
+}
+
+// d > kMaxDim: the tile sweep with the rows' weights streamed beside them
+// (where predict streams labels) and each lane's weighted list in LDS.  The
+// block's tail lanes sweep nothing and write nothing.
+template <typename T, int M>
+__global__ __launch_bounds__(kBlock) void dense_wkdist_kernel(
+    const T* __restrict__ Q, uint64_t m, int d, const T* __restrict__ Xc,
+    const uint32_t* __restrict__ wrow, uint64_t nc, int TC, double thr, int slots,
+    uint32_t target, double* __restrict__ out, unsigned long long* __restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int QB = (int)blockDim.x, tid = (int)threadIdx.x;
+    double* Bs = reinterpret_cast<double*>(smem);                        // [slots][QB]
+    T* Qs = reinterpret_cast<T*>(Bs + (size_t)slots * QB);               // [d][QB]
+    T* Cs = Qs + (size_t)d * QB;                                         // [TC][d]
+    uint32_t* Wi = reinterpret_cast<uint32_t*>(Cs + (size_t)TC * d);     // [slots][QB]
+    int32_t* Ws = reinterpret_cast<int32_t*>(Wi + (size_t)slots * QB);   // [TC]
+    stage_queries<T>(Q, m, d, Qs, bad);
+    const uint64_t gi = (uint64_t)blockIdx.x * QB + (uint64_t)tid;
+    const bool live = gi < m;
+    WLdsList list;
+    list.init(reinterpret_cast<const uint32_t*>(Ws), Bs, Wi, tid, QB, slots, thr);
+    tile_sweep<T, M, true>(Xc, reinterpret_cast<const int32_t*>(wrow), nc, d, TC, Qs, Cs, Ws, live,
+                           list);
+    if (live) out[gi] = list.result(target);
+}
+
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 uint64_t read_u64(Ctx& w, const unsigned long long* dev, int count, unsigned long long* host_out,
@@ -2031,7 +2277,7 @@ struct Forest {
 };
 
 template <typename T, int D, int M, typename K>
-void forest_run(Index& ix, int k, Forest& f, hipStream_t s) {
+void forest_run(Index& ix, int k, bool weighted, Forest& f, hipStream_t s) {
     Ctx& w = ix.work;
     const uint64_t n = ix.nc;
     const dim3 gn(blocks(n)), bl(kBlock);
@@ -2047,7 +2293,10 @@ void forest_run(Index& ix, int k, Forest& f, hipStream_t s) {
     hipLaunchKernelGGL(perm_check_kernel, gn, bl, 0, s, ix.lab, bj, n, tally);
     PD_HIP(hipGetLastError());
     double* cd_rec = w.arena.get<double>("mr_cd", n);
-    index_kdist(&ix, Q, ix.dtype, (int64_t)n, k, cd_rec, s);   // syncs
+    if (weighted)   // cd = cdw: the one difference of the weighted forest
+        index_kdist_weighted(&ix, Q, ix.dtype, (int64_t)n, k, cd_rec, s);
+    else
+        index_kdist(&ix, Q, ix.dtype, (int64_t)n, k, cd_rec, s);   // syncs
     unsigned long long h[5];
     read_u64(w, tally, 5, h, s);
     if (h[1])
@@ -2132,10 +2381,10 @@ void forest_run(Index& ix, int k, Forest& f, hipStream_t s) {
 
 }  // namespace
 
-void index_mreach_forest(Index* ix, int k, int32_t* u, int32_t* v, double* w, double* cd,
-                         int64_t capacity, int64_t* n_edges_host, int32_t* rounds_host,
-                         hipStream_t s) {
-    const char* who = "pd_index_mreach_forest";
+namespace {
+void mreach_forest(Index* ix, int k, bool weighted, int32_t* u, int32_t* v, double* w, double* cd,
+                   int64_t capacity, int64_t* n_edges_host, int32_t* rounds_host, hipStream_t s) {
+    const char* who = weighted ? "pd_index_mreach_forest_weighted" : "pd_index_mreach_forest";
     if (n_edges_host) *n_edges_host = 0;
     if (rounds_host) *rounds_host = 0;
     if (k < 1) throw Error(-1, std::string(who) + ": k must be >= 1");
@@ -2154,11 +2403,29 @@ void index_mreach_forest(Index* ix, int k, int32_t* u, int32_t* v, double* w, do
         *ix,
         [&](auto T, auto D, auto M, auto K) {
             forest_run<typename decltype(T)::type, decltype(D)::value, decltype(M)::value,
-                       typename decltype(K)::type>(*ix, k, f, s);
+                       typename decltype(K)::type>(*ix, k, weighted, f, s);
         },
         [&](auto, auto) { throw Error(-5, std::string(who) + ": d > 4"); });
     if (n_edges_host) *n_edges_host = f.edges;
     if (rounds_host) *rounds_host = f.rounds;
+}
+}  // namespace
+
+void index_mreach_forest(Index* ix, int k, int32_t* u, int32_t* v, double* w, double* cd,
+                         int64_t capacity, int64_t* n_edges_host, int32_t* rounds_host,
+                         hipStream_t s) {
+    mreach_forest(ix, k, false, u, v, w, cd, capacity, n_edges_host, rounds_host, s);
+}
+
+void index_mreach_forest_weighted(Index* ix, int k, int32_t* u, int32_t* v, double* w, double* cd,
+                                  int64_t capacity, int64_t* n_edges_host, int32_t* rounds_host,
+                                  hipStream_t s) {
+    if (n_edges_host) *n_edges_host = 0;
+    if (rounds_host) *rounds_host = 0;
+    if (!ix->weighted)
+        throw Error(-1, "pd_index_mreach_forest_weighted: the index has no weights "
+                        "(pd_index_set_weights)");
+    mreach_forest(ix, k, true, u, v, w, cd, capacity, n_edges_host, rounds_host, s);
 }
 
 // Labels of the cut: the components of the first n_prefix edges, on the member
@@ -2201,6 +2468,7 @@ Index* index_build(int device, const void* X, int dtype, int64_t n, int d, const
     ix->d = d;
     ix->metric = metric;
     ix->eps = eps;
+    ix->n_rows = (uint64_t)n;
     // fp32 screening band (see Pred): thresholds rounded outward
     const double thr = metric == 0 ? eps * eps : eps;
     if (dtype == 0 && thr > 1e-30 && thr < 1e30) {
@@ -2290,6 +2558,106 @@ void index_kdist(Index* ix, const void* Q, int dtype, int64_t m, int k, double* 
                     launch(dense_kdist_kernel<Tq, decltype(M)::value>, "dense_kdist_kernel", um,
                            p.QB, p.lds, s, (const Tq*)Q, um, ix->d, (const Tq*)ix->Xs, ix->nc, p.TC,
                            thr, k, out, bad);
+                });
+        });
+}
+
+// The rows' weights for pd_index_kdist_weighted and the weighted forest: the
+// train's fixed point and validity rule, gathered into the index's own order.
+// One host read: invalid weights, labels that are no permutation of the row
+// numbers, the smallest non-zero weight.
+void index_set_weights(Index* ix, const double* weight, hipStream_t s) {
+    const char* who = "pd_index_set_weights";
+    const uint64_t n = ix->nc;
+    if (n != ix->n_rows)
+        throw Error(-1, std::string(who) + ": the index must hold every row (build it with "
+                                           "core = ones and labels[i] = i)");
+    if (n > 0x7FFFFFFFull) throw Error(-5, std::string(who) + ": n must be <= 2^31 - 1");
+    ix->weighted = false;   // until the new weights are known to be good
+    ix->wmin = 0;
+    if (n == 0) {
+        ix->weighted = true;
+        return;
+    }
+    if (!weight) throw Error(-1, std::string(who) + ": null sample_weight");
+    Ctx& w = ix->work;
+    const dim3 gn(blocks(n)), bl(kBlock);
+    uint64_t* W = w.arena.get<uint64_t>("sw_fix", n);
+    int32_t* owner = w.arena.get<int32_t>("sw_owner", n);
+    unsigned long long* stats = w.arena.get<unsigned long long>("sw_stats", 3);
+    ix->wrec = ix->keep.get<uint32_t>("wrec", n);
+    PD_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), s));
+    PD_HIP(hipMemsetAsync(stats + 2, 0xFF, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(index_weight_fix_kernel, gn, bl, 0, s, weight, n, W, stats);
+    hipLaunchKernelGGL(index_weight_gather_kernel, gn, bl, 0, s, (const uint64_t*)W, ix->lab, n,
+                       ix->wrec, owner, stats);
+    hipLaunchKernelGGL(perm_check_kernel, gn, bl, 0, s, ix->lab, (const int32_t*)owner, n, stats);
+    PD_HIP(hipGetLastError());
+    unsigned long long h[3];
+    read_u64(w, stats, 3, h, s);   // syncs
+    if (h[1])
+        throw Error(-1, std::string(who) + ": the index's labels are not its row numbers (build "
+                                           "it with labels[i] = i)");
+    if (h[0])
+        throw Error(-1, "sample_weight: " + std::to_string(h[0]) +
+                            " value(s) not finite or outside [0, 2^31]");
+    ix->wmin = h[2] == ~0ull ? 0 : (uint64_t)h[2];
+    ix->weighted = true;
+}
+
+// pd_index_kdist's twin over the weights.  No short cut for an index with fewer
+// than k rows: one heavy row can be enough.  Without a positive weight nothing
+// ever crosses: every query gets +inf.
+void index_kdist_weighted(Index* ix, const void* Q, int dtype, int64_t m, int k, double* out,
+                          hipStream_t s) {
+    const char* who = "pd_index_kdist_weighted";
+    check_args(*ix, dtype, m, who, &k);
+    if (!ix->weighted)
+        throw Error(-1, std::string(who) + ": the index has no weights (pd_index_set_weights)");
+    const uint64_t target = (uint64_t)k << kWeightBits;
+    const uint64_t nslots = ix->wmin ? (target + ix->wmin - 1) / ix->wmin : 1;
+    if (nslots > (uint64_t)kKdistMaxK)
+        throw Error(-5, std::string(who) + ": min_samples = " + std::to_string(k) +
+                            " with the smallest positive sample_weight " +
+                            std::to_string((double)ix->wmin / (double)(1u << kWeightBits)) +
+                            " needs a list of " + std::to_string(nslots) +
+                            " slots per query; the limit is 64 (PD_KDIST_MAX_K)");
+    if (m == 0) return;
+    const uint64_t um = (uint64_t)m;
+    const int slots = (int)nslots;
+    const double thr = threshold(*ix);
+    constexpr size_t kSlot = sizeof(double) + sizeof(uint32_t);   // a pair
+    run_checked(
+        *ix, Q, um, ix->nc == 0 || ix->wmin == 0, who, s,
+        [&](unsigned long long*) {
+            hipLaunchKernelGGL(fill_f64_kernel, dim3(blocks(um)), dim3(kBlock), 0, s, out, um,
+                               (double)INFINITY);
+            PD_HIP(hipGetLastError());
+        },
+        [&](unsigned long long* bad) {
+            dispatch(
+                *ix,
+                [&](auto T, auto D, auto M, auto K) {
+                    using Tq = typename decltype(T)::type;
+                    using Kq = typename decltype(K)::type;
+                    constexpr int Dv = decltype(D)::value, Mv = decltype(M)::value;
+                    const uint32_t* order = query_order<Tq, Dv, Kq>(*ix, (const Tq*)Q, um, s);
+                    for_k_tier(slots, [&](auto KT, int lanes) {
+                        constexpr int KTv = decltype(KT)::value;
+                        const size_t lds = KTv > 0 ? 0 : (size_t)slots * lanes * kSlot;
+                        launch(wkdist_kernel<Tq, Dv, Mv, Kq, KTv>, "wkdist_kernel", um, lanes, lds,
+                               s, (const Tq*)Q, um, order, view_of<Tq, Kq>(*ix),
+                               (const uint32_t*)ix->wrec, thr, slots, (uint32_t)target, out, bad);
+                    });
+                },
+                [&](auto T, auto M) {
+                    using Tq = typename decltype(T)::type;
+                    const TilePlan p = plan_tiles(*ix, (size_t)slots * kSlot, 4, 48u << 10, true,
+                                                  who);
+                    launch(dense_wkdist_kernel<Tq, decltype(M)::value>, "dense_wkdist_kernel", um,
+                           p.QB, p.lds, s, (const Tq*)Q, um, ix->d, (const Tq*)ix->Xs,
+                           (const uint32_t*)ix->wrec, ix->nc, p.TC, thr, slots, (uint32_t)target,
+                           out, bad);
                 });
         });
 }

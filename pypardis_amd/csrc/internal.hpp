@@ -376,6 +376,14 @@ void index_radius_fill(Index* ix, const void* Q, int dtype, int64_t m, double ra
 void index_mreach_forest(Index* ix, int k, int32_t* u, int32_t* v, double* w, double* cd,
                          int64_t capacity, int64_t* n_edges_host, int32_t* rounds_host,
                          hipStream_t s);
+// sample_weight on such an index: the rows' weights, the
+// weighted core accumulator and the forest built on it.
+void index_set_weights(Index* ix, const double* weight, hipStream_t s);
+void index_kdist_weighted(Index* ix, const void* Q, int dtype, int64_t m, int k, double* out,
+                          hipStream_t s);
+void index_mreach_forest_weighted(Index* ix, int k, int32_t* u, int32_t* v, double* w, double* cd,
+                                  int64_t capacity, int64_t* n_edges_host, int32_t* rounds_host,
+                                  hipStream_t s);
 int64_t forest_labels(Ctx& ctx, int64_t n, const int32_t* u, const int32_t* v, int64_t n_prefix,
                       const uint8_t* member, int32_t* labels, hipStream_t s);
 // HDBSCAN from such a forest (hdbscan.hip): the condensed tree

@@ -296,22 +296,66 @@ def _check_kdist_args(k, r_max):
     return int(k), float(r_max)
 
 
-def _k_distances(X, q, k, r_max, metric, squared):
+def _row_weights(sample_weight, data=None):
+    """sample_weight of an index query as a 1-D float64 tensor (array, list or
+    tensor, as ``DBSCAN._weights`` takes them), wherever it lives.  Where the
+    number of rows of ``data`` is known without touching the device (an array
+    or a tensor) the length is checked here, before any device work."""
+    w = sample_weight
+    if isinstance(w, torch.Tensor):
+        w = w.detach()
+    else:
+        w = torch.from_numpy(np.ascontiguousarray(np.asarray(w, dtype=np.float64)))
+    n = data.shape[0] if isinstance(data, (torch.Tensor, np.ndarray)) else None
+    if w.dim() != 1 or (n is not None and w.shape[0] != n):
+        raise ValueError(f"sample_weight must hold one value per row: got shape "
+                         f"{tuple(w.shape)}" + ("" if n is None else f" for {n} rows"))
+    return w
+
+
+def _place_weights(w, X):
+    """The weights beside the rows of ``X``: float64, contiguous, its device."""
+    if w.shape[0] != X.shape[0]:
+        raise ValueError(f"sample_weight must hold one value per row: got shape "
+                         f"{tuple(w.shape)} for {X.shape[0]} rows")
+    if X.shape[0] > 2**31 - 1:
+        raise ValueError(f"sample_weight: {X.shape[0]} rows do not fit int32 row numbers")
+    return w.to(device=X.device, dtype=torch.float64).contiguous()
+
+
+def _weight_error(e):
+    """An invalid weight (found on the device) and a list that would need more
+    than 64 slots are the caller's ValueError."""
+    return (e.code in (_native.PD_EINVAL, _native.PD_EUNSUPPORTED)
+            and "sample_weight" in str(e))
+
+
+def _k_distances(X, q, k, r_max, metric, squared, weight=None):
     """kdist of the rows of ``q`` against the rows of ``X`` (device tensors):
-    the index over all of X is built, asked once and closed."""
+    the index over all of X is built, asked once and closed.  ``weight``: the
+    rows' weights (``_place_weights``), for the weighted core distance."""
     if q.shape[1] != X.shape[1]:
         raise ValueError(f"k_distances: queries have {q.shape[1]} coordinates, the data "
                          f"{X.shape[1]}")
     if q.dtype != X.dtype:
         q = q.to(X.dtype)
     try:
-        index = _native.Index.over_all(X, r_max, metric)
+        if weight is None:
+            index = _native.Index.over_all(X, r_max, metric)
+        else:
+            index = _native.Index.over_rows(X, r_max, metric)
         try:
-            acc = index.kdist(q, k)
+            if weight is None:
+                acc = index.kdist(q, k)
+            else:
+                index.set_weights(weight)
+                acc = index.kdist_weighted(q, k)
         finally:
             index.close()
     except _native.PardisError as e:
         if e.code == _native.PD_EINVAL and "NaN" in str(e):   # sklearn's ValueError
+            raise ValueError(str(e)) from None
+        if weight is not None and _weight_error(e):
             raise ValueError(str(e)) from None
         raise
     if squared or metric != _native.PD_EUCLIDEAN:
@@ -319,7 +363,8 @@ def _k_distances(X, q, k, r_max, metric, squared):
     return torch.sqrt(acc)
 
 
-def k_distances(data, k, r_max, metric='euclidean', queries=None, squared=False, device=None):
+def k_distances(data, k, r_max, metric='euclidean', queries=None, squared=False, device=None,
+                sample_weight=None):
     """
     :param data: the indexed points, in any form ``DBSCAN.train`` takes
     :param k: which neighbour (1 <= k <= 64); a query that is itself a row of
@@ -331,6 +376,14 @@ def k_distances(data, k, r_max, metric='euclidean', queries=None, squared=False,
         ``predict``); None: the data itself
     :param squared: euclidean only: return the squared distances — the native,
         bit-reproducible accumulator — instead of their square roots
+    :param sample_weight: None, or one weight per row of ``data`` (array, list
+        or tensor; finite, 0 <= w <= 2**31), as ``DBSCAN.train`` takes them:
+        the result is then the weighted core distance — the distance at which
+        the weights of the rows, nearest first, sum to ``k`` (a query that is a
+        row counts its own weight; a zero-weight row counts nothing).  With
+        multiplicities it is ``k_distances`` of the repeated rows.  Fewer than
+        2^31 rows; ``k`` divided by the smallest positive weight may not pass
+        64 (``ValueError``)
     :return: device float64 tensor in query order: the distance to the k-th
         nearest row of ``data``, ``inf`` where fewer than k rows lie within
         ``r_max``
@@ -340,14 +393,18 @@ def k_distances(data, k, r_max, metric='euclidean', queries=None, squared=False,
     Exact: the accumulator is the train's own (fp64, axis order, every product
     and sum rounded separately), so for any ``eps <= r_max`` a train with
     ``min_samples = k`` marks point i core exactly when ``k_distances(...,
-    squared=True)[i] <= eps * eps`` (cityblock: ``<= eps``).  The cost grows
-    with the number of rows within ``r_max``.  Single device.
+    squared=True)[i] <= eps * eps`` (cityblock: ``<= eps``) — with
+    ``sample_weight`` a train with the same weights, whose fixed-point sum the
+    weighted distance uses.  The cost grows with the number of rows within
+    ``r_max``.  Single device.
     """
     k, r_max = _check_kdist_args(k, r_max)
     metric = _native.metric_code(metric)
+    w = None if sample_weight is None else _row_weights(sample_weight, data)
     X = as_points(data, device).X
     q = X if queries is None else as_points(queries, X.device).X
-    return _k_distances(X, q, k, r_max, metric, squared)
+    return _k_distances(X, q, k, r_max, metric, squared,
+                        None if w is None else _place_weights(w, X))
 
 
 RadiusNeighbors = collections.namedtuple("RadiusNeighbors", ["indptr", "indices", "distances"])
@@ -518,9 +575,11 @@ class ReachabilityForest(collections.namedtuple(
     """What ``mutual_reachability_forest`` returns: the four device tensors,
     and beside them what ``dbscan_labels`` needs to cut the forest: ``r_max``,
     ``metric``, ``squared`` and the native accumulators (``accumulators``,
-    ``core_accumulators``: the distances before any square root)."""
+    ``core_accumulators``: the distances before any square root).
+    ``sample_weight``: None, or the float64 device tensor of the rows' weights
+    the forest was built with."""
 
-    def __new__(cls, u, v, acc, core_acc, r_max, metric, squared):
+    def __new__(cls, u, v, acc, core_acc, r_max, metric, squared, sample_weight=None):
         root = not squared and metric == _native.PD_EUCLIDEAN
         self = super().__new__(cls, u, v, torch.sqrt(acc) if root else acc,
                                torch.sqrt(core_acc) if root else core_acc)
@@ -529,30 +588,36 @@ class ReachabilityForest(collections.namedtuple(
         self.r_max = float(r_max)
         self.metric = metric
         self.squared = bool(squared)
+        self.sample_weight = sample_weight
         return self
 
 
-def _mreach_forest(X, k, r_max, metric, squared):
+def _mreach_forest(X, k, r_max, metric, squared, weight=None):
     """The forest of the rows of ``X`` (a device tensor): the index over all
-    rows is built, asked once and closed."""
+    rows is built, asked once and closed.  ``weight``: the rows' weights
+    (``_place_weights``), for the forest over the weighted core distances."""
     if X.shape[1] > 4:
         raise ValueError(f"mutual_reachability_forest: d = {X.shape[1]} is not supported: the "
                          "forest needs the cell grid of d <= 4")
     try:
         index = _native.Index.over_rows(X, r_max, metric)
         try:
-            u, v, acc, cd, _ = index.mreach_forest(k)
+            if weight is not None:
+                index.set_weights(weight)
+            u, v, acc, cd, _ = index.mreach_forest(k, weighted=weight is not None)
         finally:
             index.close()
     except _native.PardisError as e:
         if e.code == _native.PD_EINVAL and "NaN" in str(e):   # sklearn's ValueError
             raise ValueError(str(e)) from None
+        if weight is not None and _weight_error(e):
+            raise ValueError(str(e)) from None
         raise
-    return ReachabilityForest(u, v, acc, cd, r_max, metric, squared)
+    return ReachabilityForest(u, v, acc, cd, r_max, metric, squared, weight)
 
 
 def mutual_reachability_forest(data, min_samples, r_max, metric='euclidean', squared=False,
-                               device=None):
+                               device=None, sample_weight=None):
     """
     :param data: the points, in any form ``DBSCAN.train`` takes (d <= 4, fewer
         than 2^31 of them)
@@ -562,6 +627,9 @@ def mutual_reachability_forest(data, min_samples, r_max, metric='euclidean', squ
     :param metric: 'euclidean' or 'cityblock' (string or scipy callable)
     :param squared: euclidean only: return the squared distances — the native,
         bit-reproducible accumulator — instead of their square roots
+    :param sample_weight: None, or one weight per row, as ``k_distances`` takes
+        them: the core distances are then the weighted ones, everything else
+        is unchanged
     :return: ``ReachabilityForest(u, v, distances, core_distances)`` of device
         tensors: int32 ``u < v`` and float64 ``distances`` of the E edges,
         ascending by (distance, u, v), and float64[n] ``core_distances``
@@ -576,12 +644,19 @@ def mutual_reachability_forest(data, min_samples, r_max, metric='euclidean', squ
     (isolated rows included).  The list is the single-linkage merge order of
     HDBSCAN's hierarchy, and for every ``eps <= r_max`` its prefix with
     ``distance <= eps`` is the clustering of ``DBSCAN(eps, min_samples)`` on
-    the core points: see ``dbscan_labels``.  Single device.
+    the core points: see ``dbscan_labels``.  With ``sample_weight`` that holds
+    for ``DBSCAN(eps, min_samples).train(data, sample_weight=...)``; on distinct
+    rows with their multiplicities the forest is the one of the repeated rows
+    without the edges that tie a row's copies together (each at the row's core
+    distance), so multiplicities of ``min_samples`` or more give no edge of
+    distance 0.  Single device.
     """
     k, r_max = _check_kdist_args(min_samples, r_max)
     metric = _native.metric_code(metric)
+    w = None if sample_weight is None else _row_weights(sample_weight, data)
     X = as_points(data, device).X
-    return _mreach_forest(X, k, r_max, metric, squared)
+    return _mreach_forest(X, k, r_max, metric, squared,
+                          None if w is None else _place_weights(w, X))
 
 
 def dbscan_labels(forest, eps, squared=False):
@@ -656,10 +731,17 @@ def condensed_tree(forest, min_cluster_size, timings=False):
     so the tree is one defined, bit-reproducible result; another
     implementation may break tied merges differently.  An edge of distance 0
     (``min_samples`` or more identical rows) makes lambda infinite and raises
-    ``ValueError``: deduplicate the rows, or train on the distinct ones with
-    ``sample_weight``.  Single device.
+    ``ValueError``: deduplicate the rows.  A forest built with
+    ``sample_weight`` raises ``ValueError`` too: ``mutual_reachability_forest``
+    takes the distinct rows with their multiplicities and ``dbscan_labels`` cuts
+    that forest, but row weights in the condensed tree are not supported yet (a
+    cluster's size would have to be its rows' weight).  Single device.
     """
     m = _check_min_cluster_size(min_cluster_size)
+    if getattr(forest, "sample_weight", None) is not None:
+        raise ValueError("condensed_tree: the forest was built with sample_weight; row weights "
+                         "in the condensed tree are not supported yet (dbscan_labels cuts a "
+                         "weighted forest)")
     n = forest.core_accumulators.shape[0]
     try:
         raw = _native.forest_condense(n, forest.u, forest.v, forest.accumulators,
@@ -819,6 +901,7 @@ class DBSCAN(object):
         self.labels_ = None
         self.core_sample_mask_ = None
         self.n_clusters_ = None
+        self.sample_weight_ = None   # the last train's weights (device float64), or None
         self.partitioner = None
         self.shard = None
         self._points = None      # the training points (predict's index is built from them)
@@ -880,6 +963,7 @@ class DBSCAN(object):
                 raise ValueError("sample_weight is single-device: not supported with n_gpus > 1")
         self._drop_index()
         self._points = None
+        self.sample_weight_ = None
         self._trained = (float(self.eps), metric)
         group = self._process_group()
         self._group_trained = group is not None
@@ -925,6 +1009,7 @@ class DBSCAN(object):
         self.labels_ = labels
         self.core_sample_mask_ = core
         self.n_clusters_ = ncl
+        self.sample_weight_ = weight
         self.result = _Assignments(points, labels)
         self._points = points
         return self
@@ -988,13 +1073,28 @@ class DBSCAN(object):
             self._index = _native.Index(X, self.core_sample_mask_, self.labels_, eps, metric)
         return self._index.query(q)
 
-    def k_distances(self, data=None, k=None, r_max=None, squared=False):
+    def _query_weights(self, sample_weight, data, who):
+        """An explicit ``sample_weight=`` of a model query: it belongs to
+        ``data``, which must be given and is then the indexed set."""
+        if sample_weight is None:
+            return None
+        if data is None:
+            raise ValueError(f"{who}: sample_weight needs data (its rows are what the weights "
+                             "belong to); after a weighted train the train's weights are used "
+                             "when neither is given")
+        return _row_weights(sample_weight, data)
+
+    def k_distances(self, data=None, k=None, r_max=None, squared=False, sample_weight=None):
         """
         :param data: query points, in any form ``train`` takes; None: the
             training points against themselves
         :param k: default ``min_samples``
         :param r_max: default ``eps``
         :param squared: as the module-level ``k_distances``
+        :param sample_weight: one weight per row of ``data`` (which is then
+            required, and is the indexed set and the queries); None: after a
+            train with ``sample_weight`` the train's weights (``sample_weight_``)
+            beside the training points, else unweighted
         :return: as ``k_distances(points, k, r_max, metric)``: device float64,
             the distance of each query to its k-th nearest point (itself
             included), ``inf`` beyond ``r_max``
@@ -1002,7 +1102,10 @@ class DBSCAN(object):
         After a train the indexed set is the training points, and with the
         defaults ``core_sample_mask_ == (k_distances() <= eps)`` up to the
         rounding of the square root (exactly with ``squared=True`` against
-        ``eps * eps``).  Before any train ``data`` is required and is both the
+        ``eps * eps``) — also after ``train(..., sample_weight=w)``, whose
+        weights the indexed training points then carry: the result is the
+        weighted core distance, for the training points and for other
+        ``data`` alike.  Before any train ``data`` is required and is both the
         indexed set and the queries.  After a ``group=`` train each rank holds
         only its slice, so ``data=None`` raises; a given ``data`` is then
         answered against itself.  The index is built and closed per call.
@@ -1010,20 +1113,27 @@ class DBSCAN(object):
         k, r_max = _check_kdist_args(self.min_samples if k is None else k,
                                      self.eps if r_max is None else r_max)
         metric = _native.metric_code(self.metric)
+        w = self._query_weights(sample_weight, data, "k_distances")
         have = self._points is not None and not self._group_trained
-        if data is None:
+        if w is not None:
+            X = q = as_points(data, self.device).X
+            weight = _place_weights(w, X)
+        elif data is None:
             if self._group_trained:
                 raise ValueError("k_distances() after a group= train needs data: each rank "
                                  "holds only its slice of the points")
             if not have:
                 raise ValueError("k_distances before train needs data")
             X = q = self._points.X
+            weight = self.sample_weight_
         elif have:
             X = self._points.X
             q = as_points(data, X.device).X
+            weight = self.sample_weight_
         else:
             X = q = as_points(data, self.device).X
-        return _k_distances(X, q, k, r_max, metric, squared)
+            weight = None
+        return _k_distances(X, q, k, r_max, metric, squared, weight)
 
     def kneighbors(self, data=None, k=None, r_max=None, return_distance=True, squared=False):
         """
@@ -1044,7 +1154,9 @@ class DBSCAN(object):
         any train ``data`` is required and is both the indexed set and the
         queries.  After a ``group=`` train each rank holds only its slice, so
         ``data=None`` raises; a given ``data`` is then answered against
-        itself.  The index is built and closed per call.
+        itself.  The index is built and closed per call.  Unweighted, also
+        after a train with ``sample_weight`` (the identity above then holds
+        for ``k_distances()`` only).
         """
         k, r_max = _check_kdist_args(self.min_samples if k is None else k,
                                      self.eps if r_max is None else r_max)
@@ -1064,19 +1176,25 @@ class DBSCAN(object):
             X = q = as_points(data, self.device).X
         return _kneighbors(X, q, k, r_max, metric, return_distance, squared)
 
-    def mutual_reachability_forest(self, data=None, min_samples=None, r_max=None, squared=False):
+    def mutual_reachability_forest(self, data=None, min_samples=None, r_max=None, squared=False,
+                                   sample_weight=None):
         """
         :param data: the points, in any form ``train`` takes; None: the
             training points
         :param min_samples: default the model's ``min_samples``
         :param r_max: default ``eps``
         :param squared: as the module-level ``mutual_reachability_forest``
+        :param sample_weight: one weight per row of ``data`` (which is then
+            required); None: with ``data=None`` after a train with
+            ``sample_weight`` the train's weights, else unweighted
         :return: as ``mutual_reachability_forest(points, min_samples, r_max,
             metric)``: ``ReachabilityForest(u, v, distances, core_distances)``
 
         After a train, with the defaults, ``dbscan_labels(forest, eps)`` equals
         ``labels_`` on the core rows and is -1 elsewhere, and every smaller
-        ``eps`` is another cut of the same forest, with no retrain.  Before any
+        ``eps`` is another cut of the same forest, with no retrain — also after
+        ``train(..., sample_weight=w)``: the forest is then built on the weighted
+        core distances (``forest.sample_weight`` holds the weights).  Before any
         train ``data`` is required.  After a ``group=`` train each rank holds
         only its slice, so ``data=None`` raises; given ``data`` is answered on
         its own.  The index is built and closed per call.
@@ -1084,6 +1202,8 @@ class DBSCAN(object):
         k, r_max = _check_kdist_args(self.min_samples if min_samples is None else min_samples,
                                      self.eps if r_max is None else r_max)
         metric = _native.metric_code(self.metric)
+        w = self._query_weights(sample_weight, data, "mutual_reachability_forest")
+        weight = None
         if data is None:
             if self._group_trained:
                 raise ValueError("mutual_reachability_forest() after a group= train needs data: "
@@ -1091,9 +1211,12 @@ class DBSCAN(object):
             if self._points is None:
                 raise ValueError("mutual_reachability_forest before train needs data")
             X = self._points.X
+            weight = self.sample_weight_
         else:
             X = as_points(data, self.device).X
-        return _mreach_forest(X, k, r_max, metric, squared)
+            if w is not None:
+                weight = _place_weights(w, X)
+        return _mreach_forest(X, k, r_max, metric, squared, weight)
 
     def hdbscan(self, min_cluster_size, data=None, min_samples=None, r_max=None,
                 cluster_selection_method='eom', allow_single_cluster=False, return_tree=False):
@@ -1109,7 +1232,9 @@ class DBSCAN(object):
             with ``return_tree`` also the ``CondensedTree``
 
         The rules for ``data`` are ``mutual_reachability_forest``'s: before any
-        train, and after a ``group=`` train, it is required.
+        train, and after a ``group=`` train, it is required.  Unweighted, also
+        after a train with ``sample_weight``: every row counts once (row
+        weights in the condensed tree are not supported yet).
         """
         metric = _native.metric_code(self.metric)
         if data is None:
